@@ -2,7 +2,14 @@
 """bench.py -- BASELINE.json metric: CookTorrance eval+pdf pairs/s, 100M pairs per GPU, f32.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--scaling weak|strong] [--pairs P] [--model NAME]
-                    [--no-cpu] [--workload evalpdf|models|sample|fit|f64|lambertian-cpu|selftest]
+                    [--full [--no-cpu] [--no-exact]] [--dump-outputs DIR]
+                    [--workload evalpdf|models|sample|fit|f64|lambertian-cpu|selftest]
+
+A plain run (no --full) of the default workload sets up, warms up, times the K steps and prints the result line.
+--full adds the legs that take runs of their own: the exact-subnormal mode's timing and the cpu_baseline.
+--dump-outputs DIR writes what the last timed step left in the output buffers (DIR/rgb.npy, DIR/pdf.npy, f32;
+above 4M pairs a fixed, seeded sample of the pairs): the inputs are a pure function of the arguments, so two builds
+can be compared output for output.
 
 One step = one fused eval+pdf pass (bbm_hip_eval_pdf) of the model over the GPU's shard of synthetic
 direction pairs already resident in HBM (SoA f32, generated on the device by the counter-based
@@ -21,7 +28,7 @@ is launched on; algorithmic bytes = 40 B/pair (6 x 4 B in + 3 x 4 B RGB + 4 B pd
 peak = 8 TB/s HBM3E (MI355X_MICROARCH.md).  traffic: PMC-measured HBM bytes per launch from profiles/
 (see DESIGN.md §5), or null.
 
-cpu_baseline (rank 0, N=1 only): the reference itself (oracle/_ref/libbbm_ref.so: the reference headers
+cpu_baseline (--full; rank 0, N=1 only): the reference itself (oracle/_ref/libbbm_ref.so: the reference headers
 compiled with the native floatRGB backbone, OpenMP over every host thread this process may run on) on a
 bounded sample of the same pairs (copied back from the GPU), repeated for ~10 s.
 
@@ -65,8 +72,14 @@ def parse(argv=None):
     ap.add_argument("--model", default="CookTorrance")
     ap.add_argument("--models", default=None, help="comma-separated subset of models for --workload models|sample "
                                                    "(counter passes profile one model at a time)")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline leg")
-    ap.add_argument("--no-exact", action="store_true", help="evalpdf, sample: skip the exact mode's timing")
+    ap.add_argument("--full", action="store_true",
+                    help="evalpdf: after the headline's timed steps also time the exact-subnormal mode and the "
+                         "cpu_baseline (both are extra runs; off by default)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="evalpdf: write the outputs of the last timed step to DIR/rgb.npy and DIR/pdf.npy (f32; a fixed, "
+                         "seeded sample of the pairs when the batch is above 4M pairs)")
+    ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline leg (evalpdf: of --full)")
+    ap.add_argument("--no-exact", action="store_true", help="evalpdf (with --full), sample: skip the exact mode's timing")
     ap.add_argument("--cpu-seconds", type=float, default=10.0)
     ap.add_argument("--graph", default="auto", choices=["auto", "on", "off"],
                     help="evalpdf: time the K steps as HIP-graph replays of R launches (K/R replays, R | K) instead of "
@@ -120,6 +133,23 @@ def cpu_baseline(model, din, dout, seconds):
                       f"OpenMP {threads} threads = every CPU this process may use (affinity mask: {aff} threads on "
                       f"{phys} physical cores x {smt} SMT{'' if quota is None else f'; cgroup CPU quota {quota:g} CPUs'}) "
                       f"on {cpu_model}"}
+
+
+DUMP_MAX_PAIRS = 4_000_000    # 4 f32 per pair: 64 MB at the most
+
+
+def dump_outputs(path, rgb, pdf, rank, world):
+    """rgb (3, n) and pdf (n,) of the last timed step as .npy (f32).  Above DUMP_MAX_PAIRS pairs: the pairs at a fixed,
+    seeded, sorted index sample (the same indices for the same n)."""
+    n = pdf.shape[0]
+    if n > DUMP_MAX_PAIRS:
+        idx = np.sort(np.random.default_rng(SEED).integers(0, n, size=DUMP_MAX_PAIRS, dtype=np.int64))
+        idx = torch.from_numpy(idx).to(pdf.device)
+        rgb, pdf = rgb.index_select(1, idx), pdf.index_select(0, idx)
+    os.makedirs(path, exist_ok=True)
+    tag = "" if world == 1 else f"_rank{rank}"
+    np.save(os.path.join(path, f"rgb{tag}.npy"), rgb.cpu().numpy().astype(np.float32, copy=False))
+    np.save(os.path.join(path, f"pdf{tag}.npy"), pdf.cpu().numpy().astype(np.float32, copy=False))
 
 
 def lambertian_cpu(args):
@@ -199,6 +229,8 @@ def main(argv=None):
         # no GPU call has been made in this process: start the ranks as a child and exit with its status
         sys.exit(bh.launch(args.gpus, os.path.abspath(__file__), sys.argv[1:] if argv is None else argv))
     world, rank, local = bh.world_from_env(args.gpus)
+    if args.dump_outputs and args.workload != "evalpdf":
+        raise SystemExit("bench: --dump-outputs goes with --workload evalpdf")
     if args.workload == "lambertian-cpu":
         lambertian_cpu(args)
         return
@@ -244,11 +276,13 @@ def main(argv=None):
                                  "replays": args.steps // reps,
                                  "rank_ms_per_step": [t * 1e3 / args.steps for t in g_per]}
         elapsed, kern_ms, per_rank = g_el, g_ms / reps, g_per
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, rgb, pdf, rank, world)
 
-    # the same K steps in the exact-subnormal mode (bbm_hip_set_exact_subnormals: every lane the reference's float;
+    # --full: the same K steps in the exact-subnormal mode (bbm_hip_set_exact_subnormals: every lane the reference's float;
     # the Beckmann microfacet models only), reported beside the default mode's figure, not as the value
     exact = None
-    if world == 1 and not args.no_exact:
+    if args.full and world == 1 and not args.no_exact:
         prev = bbm_amd.set_exact_subnormals(True)
         try:
             e_el, e_ms, _, _ = bh.timed(launch, argparse.Namespace(**{**vars(args), "warmup": 5, "settle_s": 0.1}),
@@ -306,7 +340,7 @@ def main(argv=None):
         }
         if exact is not None:
             line["exact_subnormals_mode"] = exact
-        if world == 1 and not args.no_cpu:
+        if args.full and world == 1 and not args.no_cpu:
             line["cpu_baseline"] = cpu_baseline(model, din, dout, args.cpu_seconds)
         print(json.dumps(line), flush=True)
     if dist:

@@ -18,14 +18,14 @@ import pytest
 
 from tests import oracle_util as ou
 
-EXE = os.path.join(ou.ROOT, "tests", "cpp", "_build", "backbone_check")
+EXE = os.path.join(ou.ROOT, "oracle", "_ref", "cpp", "backbone_check")
 EXPORTED = 35      # BBM_EXPORT_BSDFMODEL in include/bsdfmodel/*.h and staticmodel/merl.h
 
 
 @pytest.fixture(scope="module")
 def lines():
     if not os.path.exists(EXE):
-        pytest.skip("tests/cpp/_build/backbone_check not built (needs the reference headers at build time)")
+        pytest.skip("oracle/_ref/cpp/backbone_check not built (needs the reference headers at build time)")
     r = subprocess.run([EXE], capture_output=True, text=True, timeout=120)
     assert r.returncode == 0, r.stdout[-4000:] + r.stderr[-4000:]
     return [json.loads(x) for x in r.stdout.splitlines() if x.startswith("{")]

@@ -1,5 +1,5 @@
 """The C++ checkBsdf command line on the HIP backbone (backbone/hip/bin/checkBsdf.cpp, built by tests/cpp/Makefile
-into tests/cpp/_build/checkBsdf): the reference's `key=value` CLI (bin/checkBsdf.cpp:420-479) over bbm_hip/check.h.
+into oracle/_ref/cpp/checkBsdf): the reference's `key=value` CLI (bin/checkBsdf.cpp:420-479) over bbm_hip/check.h.
 Its printed statistics equal the Python driver's (bbm_amd.check, the same kernels and draws) to the printed digits,
 and its option handling follows the reference (invalid keywords, unknown tests, missing test).
 """
@@ -15,7 +15,7 @@ from tests import oracle_util as ou
 torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
 
-EXE = os.path.join(ou.ROOT, "tests", "cpp", "_build", "checkBsdf")
+EXE = os.path.join(ou.ROOT, "oracle", "_ref", "cpp", "checkBsdf")
 NUM = r"[-+]?(?:\d+\.?\d*|\.\d+)(?:[eE][-+]?\d+)?|nan|inf"
 
 
@@ -25,7 +25,7 @@ def bbm():
     assert torch.cuda.is_available(), "GPU tests need a GPU"
     torch.cuda.set_device(0)
     if not os.path.exists(EXE):
-        pytest.skip("tests/cpp/_build/checkBsdf not built (needs the reference headers at build time)")
+        pytest.skip("oracle/_ref/cpp/checkBsdf not built (needs the reference headers at build time)")
     return bbm_amd
 
 

@@ -630,9 +630,9 @@ def test_cpp_adapter_drop_in(bbm):
     """backbone/hip C++ adapter: the same bbm::bsdfmodel<> instances (reference template API) on the
     CPU (native backbone) and through bbm::hip::{eval_pdf, sample} on the GPU (tests/cpp)."""
     import subprocess
-    exe = os.path.join(ou.ROOT, "tests", "cpp", "_build", "adapter_check")
+    exe = os.path.join(ou.ROOT, "oracle", "_ref", "cpp", "adapter_check")
     if not os.path.exists(exe):
-        pytest.skip("tests/cpp/_build/adapter_check not built (needs the reference headers at build time)")
+        pytest.skip("oracle/_ref/cpp/adapter_check not built (needs the reference headers at build time)")
     r = subprocess.run([exe], capture_output=True, text=True, timeout=300)
     os.makedirs(os.path.join(ou.ROOT, "gpurun_out"), exist_ok=True)
     with open(os.path.join(ou.ROOT, "gpurun_out", "adapter_check.jsonl"), "w") as f:
