@@ -23,6 +23,13 @@ from .merl import Merl  # noqa: E402  -- measured data: constructed from a file,
 
 __all__.append("Merl")
 
+# the image tools (renderSphere, plotBsdf).  `plot` the function takes the package attribute of its module's name:
+# reach the module's other names with `from bbm_amd.plot import ...`
+from .render import render_sphere  # noqa: E402
+from .plot import plot  # noqa: E402
+
+__all__ += ["render_sphere", "plot"]
+
 for _name in model_names():
     if _name.isidentifier() and _name != "Merl":          # Aggregate<Lambertian,X> entries are built with Aggregate(...)
         globals()[_name] = _make_ctor(_name)

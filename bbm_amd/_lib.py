@@ -5,7 +5,9 @@ bbm_amd/lib/libbbm_hip.so.  There is no fallback: if the library is missing or f
 every entry point raises, so a GPU run can never silently take a CPU path.
 """
 import ctypes
+import importlib.util
 import os
+import sys
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("BBM_HIP_LIB") or os.path.join(_HERE, "lib", "libbbm_hip.so")
@@ -72,6 +74,15 @@ SIGNATURES = {
     "bbm_hip_scratch_trim_captured": (_SZ, []),
     "bbm_hip_scratch_bytes": (_SZ, []),
     "bbm_hip_libm_eval": (_I, [_I, _P, _P, _P, _SZ, _P]),
+    "bbm_hip_render_sphere": (_I, [_I, _P, _I, _U32, _U32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "bbm_hip_plot": (_I, [_I, _P, _I, _I, _U32, _U32, _P, _U64, _F, _I, _P, _P, _U64, _P, _P, _P]),
+    "bbm_hip_plot_draws": (_I, [_U64, _U64, _SZ, _P, _P, _P]),
+    "bbm_hip_render_sphere_dirs": (_I, [_U32, _U32, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "bbm_hip_render_shade": (_I, [_SZ, _P, _P, _P, _P, _P, _P, _P]),
+    "bbm_hip_plot_dirs": (_I, [_U32, _U32, _U64, _P, _P, _U64, _P, _P, _P, _P]),
+    "bbm_hip_plot_accumulate": (_I, [_I, _U32, _U32, _U64, _F, _P, _P, _U64, _P, _P, _P, _P, _P]),
+    "bbm_hip_plot_bin": (_I, [_U32, _U32, _SZ, _P, _P, _P, _P, _I, _P, _P]),
+    "bbm_hip_plot_counts_image": (_I, [_P, _U32, _U32, _U64, _F, _P, _P]),
     "bbm_hip_loss_tree_workspace_size": (_SZ, [_I, _SZ]),
     "bbm_hip_loss_tree": (_I, [_P, _I, _P, _I, _I, _SZ, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _U32, _U32, _P, _P, _SZ,
                                _P]),
@@ -140,6 +151,11 @@ def load():
     global _lib
     if _lib is not None:
         return _lib
+    if "torch" not in sys.modules and importlib.util.find_spec("torch") is not None:
+        # A torch wheel brings its own copy of the HIP runtime.  Loaded first, its symbols serve this library too; were
+        # libbbm_hip loaded first it would bind the system runtime, and the process's second runtime finds no device
+        # (`python -m bbm_amd.render` in a fresh process: "no ROCm-capable device is detected" at the first launch).
+        import torch  # noqa: F401
     if not os.path.exists(LIB_PATH):
         raise ImportError(f"{LIB_PATH} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'`")
     lib = ctypes.CDLL(LIB_PATH)

@@ -3,6 +3,7 @@
 // per family in inst_*.hip.
 #include <hip/hip_runtime.h>
 
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -217,6 +218,7 @@ struct ModelEntry
   ReflLauncher reflectance;
   LossLauncher loss;
   CheckLauncher check;
+  ImageLauncher image;
   float defaults[kMaxParams];
   float lower[kMaxParams];
   float upper[kMaxParams];
@@ -232,88 +234,88 @@ constexpr float kFMin = 1.1754943508222875e-38f;
 // reported by parameter_lower_bound/upper_bound, ior 1.3 in [1,5]); pinned against
 // tests/golden/models.json by tests/test_abi.py.
 const ModelEntry kSingle[] = {
-  {"Lambertian", 3, kFlagDiffuse, &launch_eval_pdf<Lambertian>, &launch_sample<Lambertian>, &launch_reflectance<Lambertian>, &launch_loss<Lambertian>, &launch_check<Lambertian>,
+  {"Lambertian", 3, kFlagDiffuse, &launch_eval_pdf<Lambertian>, &launch_sample<Lambertian>, &launch_reflectance<Lambertian>, &launch_loss<Lambertian>, &launch_check<Lambertian>, &launch_image<Lambertian>,
    {0.5f, 0.5f, 0.5f}, {0, 0, 0}, {1, 1, 1}, "ddd"},
-  {"CookTorrance", 5, kFlagSpecular, &launch_eval_pdf<CookTorranceM>, &launch_sample<CookTorranceM>, &launch_reflectance<CookTorranceM>, &launch_loss<CookTorranceM>, &launch_check<CookTorranceM>,
+  {"CookTorrance", 5, kFlagSpecular, &launch_eval_pdf<CookTorranceM>, &launch_sample<CookTorranceM>, &launch_reflectance<CookTorranceM>, &launch_loss<CookTorranceM>, &launch_check<CookTorranceM>, &launch_image<CookTorranceM>,
    {0.5f, 0.5f, 0.5f, 0.1f, 1.3f}, {0, 0, 0, kEpsF, 1}, {1, 1, 1, 1, 5}, "ssspp"},
-  {"LowCookTorrance", 5, kFlagSpecular, &launch_eval_pdf<CookTorranceM>, &launch_sample<CookTorranceM>, &launch_reflectance<CookTorranceM>, &launch_loss<CookTorranceM>, &launch_check<CookTorranceM>,   // bsdfmodel/low.h:32-33
+  {"LowCookTorrance", 5, kFlagSpecular, &launch_eval_pdf<CookTorranceM>, &launch_sample<CookTorranceM>, &launch_reflectance<CookTorranceM>, &launch_loss<CookTorranceM>, &launch_check<CookTorranceM>, &launch_image<CookTorranceM>,   // bsdfmodel/low.h:32-33
    {0.5f, 0.5f, 0.5f, 0.1f, 1.3f}, {0, 0, 0, kEpsF, 1}, {1, 1, 1, 1, 5}, "ssspp"},
-  {"GGX", 5, kFlagSpecular, &launch_eval_pdf<GGXM>, &launch_sample<GGXM>, &launch_reflectance<GGXM>, &launch_loss<GGXM>, &launch_check<GGXM>,
+  {"GGX", 5, kFlagSpecular, &launch_eval_pdf<GGXM>, &launch_sample<GGXM>, &launch_reflectance<GGXM>, &launch_loss<GGXM>, &launch_check<GGXM>, &launch_image<GGXM>,
    {0.5f, 0.5f, 0.5f, 0.1f, 1.3f}, {0, 0, 0, kEpsF, 1}, {1, 1, 1, 1, 5}, "ssspp"},
-  {"CookTorranceWalter", 5, kFlagSpecular, &launch_eval_pdf<CookTorranceWalterM>, &launch_sample<CookTorranceWalterM>, &launch_reflectance<CookTorranceWalterM>, &launch_loss<CookTorranceWalterM>, &launch_check<CookTorranceWalterM>,
+  {"CookTorranceWalter", 5, kFlagSpecular, &launch_eval_pdf<CookTorranceWalterM>, &launch_sample<CookTorranceWalterM>, &launch_reflectance<CookTorranceWalterM>, &launch_loss<CookTorranceWalterM>, &launch_check<CookTorranceWalterM>, &launch_image<CookTorranceWalterM>,
    {0.5f, 0.5f, 0.5f, 0.1f, 1.3f}, {0, 0, 0, kEpsF, 1}, {1, 1, 1, 1, 5}, "ssspp"},
-  {"CookTorranceHeitz", 6, kFlagSpecular, &launch_eval_pdf<CookTorranceHeitzM>, &launch_sample<CookTorranceHeitzM>, &launch_reflectance<CookTorranceHeitzM>, &launch_loss<CookTorranceHeitzM>, &launch_check<CookTorranceHeitzM>,
+  {"CookTorranceHeitz", 6, kFlagSpecular, &launch_eval_pdf<CookTorranceHeitzM>, &launch_sample<CookTorranceHeitzM>, &launch_reflectance<CookTorranceHeitzM>, &launch_loss<CookTorranceHeitzM>, &launch_check<CookTorranceHeitzM>, &launch_image<CookTorranceHeitzM>,
    {0.5f, 0.5f, 0.5f, 0.1f, 0.1f, 1.3f}, {0, 0, 0, kEpsF, kEpsF, 1}, {1, 1, 1, 1, 1, 5}, "sssppp"},
-  {"GGXHeitz", 6, kFlagSpecular, &launch_eval_pdf<GGXHeitzM>, &launch_sample<GGXHeitzM>, &launch_reflectance<GGXHeitzM>, &launch_loss<GGXHeitzM>, &launch_check<GGXHeitzM>,
+  {"GGXHeitz", 6, kFlagSpecular, &launch_eval_pdf<GGXHeitzM>, &launch_sample<GGXHeitzM>, &launch_reflectance<GGXHeitzM>, &launch_loss<GGXHeitzM>, &launch_check<GGXHeitzM>, &launch_image<GGXHeitzM>,
    {0.5f, 0.5f, 0.5f, 0.1f, 0.1f, 1.3f}, {0, 0, 0, kEpsF, kEpsF, 1}, {1, 1, 1, 1, 1, 5}, "sssppp"},
-  {"NganCookTorrance", 5, kFlagSpecular, &launch_eval_pdf<NganCookTorranceM>, &launch_sample<NganCookTorranceM>, &launch_reflectance<NganCookTorranceM>, &launch_loss<NganCookTorranceM>, &launch_check<NganCookTorranceM>,
+  {"NganCookTorrance", 5, kFlagSpecular, &launch_eval_pdf<NganCookTorranceM>, &launch_sample<NganCookTorranceM>, &launch_reflectance<NganCookTorranceM>, &launch_loss<NganCookTorranceM>, &launch_check<NganCookTorranceM>, &launch_image<NganCookTorranceM>,
    {0.5f, 0.5f, 0.5f, 0.1f, 0.1f}, {0, 0, 0, kEpsF, 0}, {1, 1, 1, 1, 1}, "ssspp"},
-  {"PhongWalter", 5, kFlagSpecular, &launch_eval_pdf<PhongWalterM>, &launch_sample<PhongWalterM>, &launch_reflectance<PhongWalterM>, &launch_loss<PhongWalterM>, &launch_check<PhongWalterM>,
+  {"PhongWalter", 5, kFlagSpecular, &launch_eval_pdf<PhongWalterM>, &launch_sample<PhongWalterM>, &launch_reflectance<PhongWalterM>, &launch_loss<PhongWalterM>, &launch_check<PhongWalterM>, &launch_image<PhongWalterM>,
    {0.5f, 0.5f, 0.5f, 32.0f, 1.3f}, {0, 0, 0, 0, 1}, {1, 1, 1, kFMax, 5}, "ssspp"},
-  {"Ribardiere", 6, kFlagSpecular, &launch_eval_pdf<RibardiereM>, &launch_sample<RibardiereM>, &launch_reflectance<RibardiereM>, &launch_loss<RibardiereM>, &launch_check<RibardiereM>,
+  {"Ribardiere", 6, kFlagSpecular, &launch_eval_pdf<RibardiereM>, &launch_sample<RibardiereM>, &launch_reflectance<RibardiereM>, &launch_loss<RibardiereM>, &launch_check<RibardiereM>, &launch_image<RibardiereM>,
    {0.5f, 0.5f, 0.5f, 0.1f, 2.0f, 1.3f}, {0, 0, 0, kEpsF, 1.5f + kEpsF, 1}, {1, 1, 1, 1, 40, 5}, "sssppp"},
-  {"RibardiereAnisotropic", 7, kFlagSpecular, &launch_eval_pdf<RibardiereAnisoM>, &launch_sample<RibardiereAnisoM>, &launch_reflectance<RibardiereAnisoM>, &launch_loss<RibardiereAnisoM>, &launch_check<RibardiereAnisoM>,
+  {"RibardiereAnisotropic", 7, kFlagSpecular, &launch_eval_pdf<RibardiereAnisoM>, &launch_sample<RibardiereAnisoM>, &launch_reflectance<RibardiereAnisoM>, &launch_loss<RibardiereAnisoM>, &launch_check<RibardiereAnisoM>, &launch_image<RibardiereAnisoM>,
    {0.5f, 0.5f, 0.5f, 0.1f, 0.1f, 2.0f, 1.3f}, {0, 0, 0, kEpsF, kEpsF, 1.5f + kEpsF, 1}, {1, 1, 1, 1, 1, 40, 5}, "ssspppp"},
-  {"OrenNayar", 4, kFlagDiffuse, &launch_eval_pdf<OrenNayar>, &launch_sample<OrenNayar>, &launch_reflectance<OrenNayar>, &launch_loss<OrenNayar>, &launch_check<OrenNayar>,
+  {"OrenNayar", 4, kFlagDiffuse, &launch_eval_pdf<OrenNayar>, &launch_sample<OrenNayar>, &launch_reflectance<OrenNayar>, &launch_loss<OrenNayar>, &launch_check<OrenNayar>, &launch_image<OrenNayar>,
    {0.5f, 0.5f, 0.5f, 0.1f}, {0, 0, 0, kEpsF}, {1, 1, 1, 1}, "dddD"},
-  {"LowMicrofacet", 6, kFlagSpecular, &launch_eval_pdf<LowMicrofacetM>, &launch_sample<LowMicrofacetM>, &launch_reflectance<LowMicrofacetM>, &launch_loss<LowMicrofacetM>, &launch_check<LowMicrofacetM>,
+  {"LowMicrofacet", 6, kFlagSpecular, &launch_eval_pdf<LowMicrofacetM>, &launch_sample<LowMicrofacetM>, &launch_reflectance<LowMicrofacetM>, &launch_loss<LowMicrofacetM>, &launch_check<LowMicrofacetM>, &launch_image<LowMicrofacetM>,
    {1, 1, 1, 1, 1, 1.3f}, {0, 0, 0, 0, 0, 1}, {kFMax, kFMax, kFMax, kFMax, kFMax, 5}, "pppppp"},
-  {"LowMicrofacetFit", 6, kFlagSpecular, &launch_eval_pdf<LowMicrofacetM>, &launch_sample<LowMicrofacetM>, &launch_reflectance<LowMicrofacetM>, &launch_loss<LowMicrofacetM>, &launch_check<LowMicrofacetM>,
+  {"LowMicrofacetFit", 6, kFlagSpecular, &launch_eval_pdf<LowMicrofacetM>, &launch_sample<LowMicrofacetM>, &launch_reflectance<LowMicrofacetM>, &launch_loss<LowMicrofacetM>, &launch_check<LowMicrofacetM>, &launch_image<LowMicrofacetM>,
    {1, 1, 1, 1, 1, 1.3f}, {0, 0, 0, 0, 0, 1}, {kFMax, kFMax, kFMax, kFMax, kFMax, 5}, "pppppp"},
-  {"Ward", 5, kFlagSpecular, &launch_eval_pdf<WardM>, &launch_sample<WardM>, &launch_reflectance<WardM>, &launch_loss<WardM>, &launch_check<WardM>,
+  {"Ward", 5, kFlagSpecular, &launch_eval_pdf<WardM>, &launch_sample<WardM>, &launch_reflectance<WardM>, &launch_loss<WardM>, &launch_check<WardM>, &launch_image<WardM>,
    {0.5f, 0.5f, 0.5f, 0.1f, 0.1f}, {0, 0, 0, kEpsF, kEpsF}, {1, 1, 1, 1, 1}, "ssspp"},
-  {"WardDuer", 5, kFlagSpecular, &launch_eval_pdf<WardDuerM>, &launch_sample<WardDuerM>, &launch_reflectance<WardDuerM>, &launch_loss<WardDuerM>, &launch_check<WardDuerM>,
+  {"WardDuer", 5, kFlagSpecular, &launch_eval_pdf<WardDuerM>, &launch_sample<WardDuerM>, &launch_reflectance<WardDuerM>, &launch_loss<WardDuerM>, &launch_check<WardDuerM>, &launch_image<WardDuerM>,
    {0.5f, 0.5f, 0.5f, 0.1f, 0.1f}, {0, 0, 0, kEpsF, kEpsF}, {1, 1, 1, 1, 1}, "ssspp"},
-  {"WardDuerGeislerMoroder", 5, kFlagSpecular, &launch_eval_pdf<WardDGMM>, &launch_sample<WardDGMM>, &launch_reflectance<WardDGMM>, &launch_loss<WardDGMM>, &launch_check<WardDGMM>,
+  {"WardDuerGeislerMoroder", 5, kFlagSpecular, &launch_eval_pdf<WardDGMM>, &launch_sample<WardDGMM>, &launch_reflectance<WardDGMM>, &launch_loss<WardDGMM>, &launch_check<WardDGMM>, &launch_image<WardDGMM>,
    {0.5f, 0.5f, 0.5f, 0.1f, 0.1f}, {0, 0, 0, kEpsF, kEpsF}, {1, 1, 1, 1, 1}, "ssspp"},
-  {"NganWard", 4, kFlagSpecular, &launch_eval_pdf<NganWardM>, &launch_sample<NganWardM>, &launch_reflectance<NganWardM>, &launch_loss<NganWardM>, &launch_check<NganWardM>,
+  {"NganWard", 4, kFlagSpecular, &launch_eval_pdf<NganWardM>, &launch_sample<NganWardM>, &launch_reflectance<NganWardM>, &launch_loss<NganWardM>, &launch_check<NganWardM>, &launch_image<NganWardM>,
    {0.5f, 0.5f, 0.5f, 0.1f}, {0, 0, 0, kEpsF}, {1, 1, 1, 1}, "sssp"},
-  {"NganWardDuer", 4, kFlagSpecular, &launch_eval_pdf<NganWardDuerM>, &launch_sample<NganWardDuerM>, &launch_reflectance<NganWardDuerM>, &launch_loss<NganWardDuerM>, &launch_check<NganWardDuerM>,
+  {"NganWardDuer", 4, kFlagSpecular, &launch_eval_pdf<NganWardDuerM>, &launch_sample<NganWardDuerM>, &launch_reflectance<NganWardDuerM>, &launch_loss<NganWardDuerM>, &launch_check<NganWardDuerM>, &launch_image<NganWardDuerM>,
    {0.5f, 0.5f, 0.5f, 0.1f}, {0, 0, 0, kEpsF}, {1, 1, 1, 1}, "sssp"},
-  {"Phong", 4, kFlagSpecular, &launch_eval_pdf<PhongLobe>, &launch_sample<PhongLobe>, &launch_reflectance<PhongLobe>, &launch_loss<PhongLobe>, &launch_check<PhongLobe>,
+  {"Phong", 4, kFlagSpecular, &launch_eval_pdf<PhongLobe>, &launch_sample<PhongLobe>, &launch_reflectance<PhongLobe>, &launch_loss<PhongLobe>, &launch_check<PhongLobe>, &launch_image<PhongLobe>,
    {0.5f, 0.5f, 0.5f, 32.0f}, {0, 0, 0, 0}, {1, 1, 1, kFMax}, "sssp"},
-  {"NganBlinnPhong", 4, kFlagSpecular, &launch_eval_pdf<PhongLobe>, &launch_sample<PhongLobe>, &launch_reflectance<PhongLobe>, &launch_loss<PhongLobe>, &launch_check<PhongLobe>,   // ngan.h:43-44
+  {"NganBlinnPhong", 4, kFlagSpecular, &launch_eval_pdf<PhongLobe>, &launch_sample<PhongLobe>, &launch_reflectance<PhongLobe>, &launch_loss<PhongLobe>, &launch_check<PhongLobe>, &launch_image<PhongLobe>,   // ngan.h:43-44
    {0.5f, 0.5f, 0.5f, 32.0f}, {0, 0, 0, 0}, {1, 1, 1, kFMax}, "sssp"},
-  {"Lafortune", 7, kFlagSpecular, &launch_eval_pdf<LafortuneM>, &launch_sample<LafortuneM>, &launch_reflectance<LafortuneM>, &launch_loss<LafortuneM>, &launch_check<LafortuneM>,
+  {"Lafortune", 7, kFlagSpecular, &launch_eval_pdf<LafortuneM>, &launch_sample<LafortuneM>, &launch_reflectance<LafortuneM>, &launch_loss<LafortuneM>, &launch_check<LafortuneM>, &launch_image<LafortuneM>,
    {0.5f, 0.5f, 0.5f, -0.57735026919f, -0.57735026919f, 0.57735026919f, 32.0f},
    {0, 0, 0, kFMin, kFMin, kFMin, 0}, {1, 1, 1, kFMax, kFMax, kFMax, kFMax}, "ssspppp"},
-  {"NganLafortune", 6, kFlagSpecular, &launch_eval_pdf<NganLafortuneM>, &launch_sample<NganLafortuneM>, &launch_reflectance<NganLafortuneM>, &launch_loss<NganLafortuneM>, &launch_check<NganLafortuneM>,
+  {"NganLafortune", 6, kFlagSpecular, &launch_eval_pdf<NganLafortuneM>, &launch_sample<NganLafortuneM>, &launch_reflectance<NganLafortuneM>, &launch_loss<NganLafortuneM>, &launch_check<NganLafortuneM>, &launch_image<NganLafortuneM>,
    {0.5f, 0.5f, 0.5f, -0.57735026919f, 0.57735026919f, 32.0f}, {0, 0, 0, kFMin, kFMin, 0}, {1, 1, 1, kFMax, kFMax, kFMax}, "sssppp"},
-  {"AshikhminShirley", 5, kFlagSpecular, &launch_eval_pdf<ASM>, &launch_sample<ASM>, &launch_reflectance<ASM>, &launch_loss<ASM>, &launch_check<ASM>,
+  {"AshikhminShirley", 5, kFlagSpecular, &launch_eval_pdf<ASM>, &launch_sample<ASM>, &launch_reflectance<ASM>, &launch_loss<ASM>, &launch_check<ASM>, &launch_image<ASM>,
    {0.1f, 0.1f, 0.1f, 32.0f, 32.0f}, {0, 0, 0, 0, 0}, {1, 1, 1, kFMax, kFMax}, "ppppp"},
-  {"AshikhminShirleyFull", 8, kFlagAll, &launch_eval_pdf<ASFullM>, &launch_sample<ASFullM>, &launch_reflectance<ASFullM>, &launch_loss<ASFullM>, &launch_check<ASFullM>,
+  {"AshikhminShirleyFull", 8, kFlagAll, &launch_eval_pdf<ASFullM>, &launch_sample<ASFullM>, &launch_reflectance<ASFullM>, &launch_loss<ASFullM>, &launch_check<ASFullM>, &launch_image<ASFullM>,
    {0.5f, 0.5f, 0.5f, 0.1f, 0.1f, 0.1f, 32.0f, 32.0f}, {0, 0, 0, 0, 0, 0, 0, 0}, {1, 1, 1, 1, 1, 1, kFMax, kFMax}, "dddppppp"},
-  {"LowAshikhminShirley", 5, kFlagSpecular, &launch_eval_pdf<LowASM>, &launch_sample<LowASM>, &launch_reflectance<LowASM>, &launch_loss<LowASM>, &launch_check<LowASM>,
+  {"LowAshikhminShirley", 5, kFlagSpecular, &launch_eval_pdf<LowASM>, &launch_sample<LowASM>, &launch_reflectance<LowASM>, &launch_loss<LowASM>, &launch_check<LowASM>, &launch_image<LowASM>,
    {0.5f, 0.5f, 0.5f, 1.3f, 32.0f}, {0, 0, 0, 1, 0}, {1, 1, 1, 5, kFMax}, "ssspp"},
-  {"NganAshikhminShirley", 5, kFlagSpecular, &launch_eval_pdf<NganASM>, &launch_sample<NganASM>, &launch_reflectance<NganASM>, &launch_loss<NganASM>, &launch_check<NganASM>,
+  {"NganAshikhminShirley", 5, kFlagSpecular, &launch_eval_pdf<NganASM>, &launch_sample<NganASM>, &launch_reflectance<NganASM>, &launch_loss<NganASM>, &launch_check<NganASM>, &launch_image<NganASM>,
    {0.5f, 0.5f, 0.5f, 0.1f, 32.0f}, {0, 0, 0, 0, 0}, {1, 1, 1, 1, kFMax}, "ssspp"},
-  {"LowSmooth", 6, kFlagSpecular, &launch_eval_pdf<LowSmooth>, &launch_sample<LowSmooth>, &launch_reflectance<LowSmooth>, &launch_loss<LowSmooth>, &launch_check<LowSmooth>,
+  {"LowSmooth", 6, kFlagSpecular, &launch_eval_pdf<LowSmooth>, &launch_sample<LowSmooth>, &launch_reflectance<LowSmooth>, &launch_loss<LowSmooth>, &launch_check<LowSmooth>, &launch_image<LowSmooth>,
    {1, 1, 1, 1, 1, 1.3f}, {0, 0, 0, 0, 0, 1}, {kFMax, kFMax, kFMax, kFMax, kFMax, 5}, "pppppp"},
   // bsdfmodel/bagher.h:62-68: albedo, K, Lambda, c, theta0, k (ndf/sgd.h:197-203, Dependent),
   // alpha, p (sgd.h:107-111), eta = (F0, F1) RGB (bagher.h:31, default {1, 0}, lower {0, -1})
-  {"Bagher", 30, kFlagSpecular, &launch_eval_pdf<Bagher>, &launch_sample<Bagher>, &launch_reflectance<Bagher>, &launch_loss<Bagher>, &launch_check<Bagher>,
+  {"Bagher", 30, kFlagSpecular, &launch_eval_pdf<Bagher>, &launch_sample<Bagher>, &launch_reflectance<Bagher>, &launch_loss<Bagher>, &launch_check<Bagher>, &launch_image<Bagher>,
    {0.5f, 0.5f, 0.5f, 7.5f, 7.5f, 7.5f, 1, 1, 1, 1, 1, 1, 1.5707963705062866f, 1.5707963705062866f, 1.5707963705062866f,
     1, 1, 1, 0.1f, 0.1f, 0.1f, 0.64f, 0.64f, 0.64f, 1, 1, 1, 0, 0, 0},
    {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, kEpsF, kEpsF, kEpsF, 0, 0, 0, 0, 0, 0, -1, -1, -1},
    {1, 1, 1, kFMax, kFMax, kFMax, kFMax, kFMax, kFMax, kFMax, kFMax, kFMax, kFMax, kFMax, kFMax, kFMax, kFMax, kFMax,
     1, 1, 1, kFMax, kFMax, kFMax, 1, 1, 1, 1, 1, 1}, "sssxxxxxxxxxxxxxxxpppppppppppp"},
   // EPD (bsdfmodel/holzschuchpacanowski.h:34-42): beta, p (ndf/epd.h:180-182), eta = complex ior (n, k)
-  {"EPD", 4, kFlagSpecular, &launch_eval_pdf<EpdM>, &launch_sample<EpdM>, &launch_reflectance<EpdM>, &launch_loss<EpdM>, &launch_check<EpdM>,
+  {"EPD", 4, kFlagSpecular, &launch_eval_pdf<EpdM>, &launch_sample<EpdM>, &launch_reflectance<EpdM>, &launch_loss<EpdM>, &launch_check<EpdM>, &launch_image<EpdM>,
    {0.003f, 0.2f, 1.3f, 0.0f}, {0.0f, 0.0f, 0.1f, 0.0f}, {0.5f, 5.0f, 5.0f, 10.0f}, "pppp"},
   // He family (bsdfmodel/he.h:473-477, :489-496; ngan.h:166-167): roughness, autocorrelation, eta (complex RGB:
   // n RGB, k RGB; NganHe: albedo first and a scalar ior)
 #define BBM_HIP_HE_ENTRY(NAME, M)                                                                             \
-  {NAME, 8, kFlagSpecular, &launch_eval_pdf<M>, &launch_sample<M>, &launch_reflectance<M>, &launch_loss<M>, &launch_check<M>, \
+  {NAME, 8, kFlagSpecular, &launch_eval_pdf<M>, &launch_sample<M>, &launch_reflectance<M>, &launch_loss<M>, &launch_check<M>, &launch_image<M>, \
    {0.18f, 3.0f, 1.3f, 1.3f, 1.3f, 0, 0, 0}, {0, 0, 0.1f, 0.1f, 0.1f, 0, 0, 0},                                 \
    {kFMax, kFMax, 5, 5, 5, 10, 10, 10}, "pppppppp"}
   BBM_HIP_HE_ENTRY("He", HeM),
   BBM_HIP_HE_ENTRY("HeWestin", HeWestinM),
   BBM_HIP_HE_ENTRY("HeHolzschuch", HeHolzschuchM),
-  {"NganHe", 6, kFlagSpecular, &launch_eval_pdf<NganHeM>, &launch_sample<NganHeM>, &launch_reflectance<NganHeM>, &launch_loss<NganHeM>, &launch_check<NganHeM>,
+  {"NganHe", 6, kFlagSpecular, &launch_eval_pdf<NganHeM>, &launch_sample<NganHeM>, &launch_reflectance<NganHeM>, &launch_loss<NganHeM>, &launch_check<NganHeM>, &launch_image<NganHeM>,
    {0.5f, 0.5f, 0.5f, 0.18f, 3.0f, 1.3f}, {0, 0, 0, 0, 0, 1}, {1, 1, 1, kFMax, kFMax, 5}, "sssppp"},
   // Merl (staticmodel/merl.h:224-225): no attributes in the reference (the data comes from a file); the two
   // slots hold the device address of a table built by bbm_hip_merl_table, flagged Dependent so no fit moves them
-  {"Merl", 2, kFlagAll, &launch_eval_pdf<Merl>, &launch_sample<Merl>, &launch_reflectance<Merl>, &launch_loss<Merl>, &launch_check<Merl>,
+  {"Merl", 2, kFlagAll, &launch_eval_pdf<Merl>, &launch_sample<Merl>, &launch_reflectance<Merl>, &launch_loss<Merl>, &launch_check<Merl>, &launch_image<Merl>,
    {0, 0}, {0, 0}, {0, 0}, "xx"},
 };
 constexpr int kNumSingle = int(sizeof(kSingle) / sizeof(kSingle[0]));
@@ -337,10 +339,11 @@ struct AggregateSpec
   ReflLauncher reflectance;
   LossLauncher loss;
   CheckLauncher check;
+  ImageLauncher image;
 };
 #define BBM_HIP_AGG(KEY, CHILD, M) \
   {KEY, CHILD, kFlagDiffuse | M::kComponent, &launch_eval_pdf<M>, &launch_sample<M>, &launch_reflectance<M>, &launch_loss<M>, \
-   &launch_check<M>}
+   &launch_check<M>, &launch_image<M>}
 const AggregateSpec kAggregates[] = {
   BBM_HIP_AGG("Aggregate<Lambertian,Bagher>", "Bagher", AggBagherM),                      // fits/bagher_sgd.fit
   BBM_HIP_AGG("Aggregate<Lambertian,CookTorrance>", "CookTorrance", AggCookTorranceM),    // docs/source/fitting.rst:31-33
@@ -381,7 +384,7 @@ struct Registry
       e.name = g.name;
       e.nparams = lam->nparams + c->nparams;
       e.components = g.components;
-      e.eval_pdf = g.eval_pdf; e.sample = g.sample; e.reflectance = g.reflectance; e.loss = g.loss; e.check = g.check;
+      e.eval_pdf = g.eval_pdf; e.sample = g.sample; e.reflectance = g.reflectance; e.loss = g.loss; e.check = g.check; e.image = g.image;
       for (int i = 0; i < lam->nparams; ++i)
       {
         e.defaults[i] = lam->defaults[i]; e.lower[i] = lam->lower[i]; e.upper[i] = lam->upper[i];
@@ -1060,6 +1063,198 @@ int bbm_hip_check(int model_id, const float* params, int nparams, const bbm_hip_
   }
   if (d->n == 0) return BBM_HIP_OK;
   return e->check(d->test, a, acc, s);
+}
+
+// ------------------------------------------------------------------------------- image tools (image.hpp)
+
+namespace {
+// bbm::normalize on the host, in float: t * (1 / sqrt(|t|^2)) (backbone horizontal.h:105-109); false for a zero or
+// non-finite vector
+bool normalize_host(const float* v, float* o)
+{
+  if (!v) return false;
+  const float sq = ((0.0f + v[0] * v[0]) + v[1] * v[1]) + v[2] * v[2];
+  if (!std::isfinite(v[0]) || !std::isfinite(v[1]) || !std::isfinite(v[2]) || !std::isfinite(sq) || !(sq > 0.0f)) return false;
+  const float r = 1.0f / std::sqrt(sq);
+  for (int k = 0; k < 3; ++k) o[k] = v[k] * r;
+  return std::isfinite(o[0]) && std::isfinite(o[1]) && std::isfinite(o[2]);
+}
+
+int image_size(uint32_t width, uint32_t height)
+{
+  if (width == 0 || height == 0) return fail(BBM_HIP_ERR_INVALID_ARG, "image width and height must be positive");
+  if (uint64_t(width) * height > kImageMaxPixels) return fail(BBM_HIP_ERR_INVALID_ARG, "image has more than 2^31 pixels");
+  return BBM_HIP_OK;
+}
+
+// renderSphere.cpp:114, :129: light = normalize(light); render(..., -normalize(light), ...)
+int render_light(const float* light, v3& dir)
+{
+  float l1[3], l2[3];
+  if (!normalize_host(light, l1) || !normalize_host(l1, l2))
+    return fail(BBM_HIP_ERR_INVALID_ARG, "light must be a finite non-zero vector");
+  dir.x = -l2[0]; dir.y = -l2[1]; dir.z = -l2[2];
+  return BBM_HIP_OK;
+}
+
+// plotBsdf.cpp:113-142 and the draws: kind, samples, view = normalize(view), xi / key
+int plot_args(int kind, uint32_t width, uint32_t height, const float* view, uint64_t samples, float scale,
+              const float* xi0, const float* xi1, uint64_t seed, ImageArgs& a)
+{
+  if (kind != kPlotEval && kind != kPlotPdf && kind != kPlotSample) return fail(BBM_HIP_ERR_INVALID_ARG, "unknown plot kind");
+  if (const int rc = image_size(width, height)) return rc;
+  if (samples == 0) return fail(BBM_HIP_ERR_INVALID_ARG, "samples must be positive");
+  if (samples > (uint64_t(1) << 40) / (uint64_t(width) * height) + 1)
+    return fail(BBM_HIP_ERR_INVALID_ARG, "width x height x samples exceeds 2^40 draws");
+  float v[3];
+  if (!normalize_host(view, v)) return fail(BBM_HIP_ERR_INVALID_ARG, "view must be a finite non-zero vector");
+  if ((xi0 == nullptr) != (xi1 == nullptr)) return fail(BBM_HIP_ERR_INVALID_ARG, "xi0 and xi1 must both be given or both be NULL");
+  a.op = kind;
+  a.width = width; a.height = height; a.samples = samples;
+  a.dir.x = v[0]; a.dir.y = v[1]; a.dir.z = v[2];
+  a.scale = scale;
+  a.key = plot_key(seed);
+  a.xi0 = xi0; a.xi1 = xi1;
+  return BBM_HIP_OK;
+}
+}  // namespace
+
+int bbm_hip_render_sphere(int model_id, const float* params, int nparams, uint32_t width, uint32_t height,
+                          const float* light, float* image, float* in_x, float* in_y, float* in_z,
+                          float* out_x, float* out_y, float* out_z, uint8_t* mask, void* stream)
+{
+  const CallExactScope mode_scope(model_id);
+  EvalArgs tmp;
+  const ModelEntry* e;
+  int rc = prepare(model_id, params, nparams, 0, tmp, e);
+  if (rc) return rc;
+  if ((rc = image_size(width, height))) return rc;
+  if (!image) return fail(BBM_HIP_ERR_INVALID_ARG, "image pointer is NULL");
+  if ((in_x || in_y || in_z) && !(in_x && in_y && in_z)) return fail(BBM_HIP_ERR_INVALID_ARG, "in direction pointer is NULL");
+  if ((out_x || out_y || out_z) && !(out_x && out_y && out_z)) return fail(BBM_HIP_ERR_INVALID_ARG, "out direction pointer is NULL");
+  ImageArgs a;
+  std::memset(&a, 0, sizeof(a));
+  if ((rc = render_light(light, a.dir))) return rc;
+  a.op = kImageRender;
+  a.width = width; a.height = height; a.samples = 1; a.scale = 1.0f;
+  a.img = image;
+  a.ix = in_x; a.iy = in_y; a.iz = in_z; a.ox = out_x; a.oy = out_y; a.oz = out_z; a.mask = mask;
+  a.p = tmp.p;
+  return e->image(a, static_cast<hipStream_t>(stream));
+}
+
+int bbm_hip_render_sphere_dirs(uint32_t width, uint32_t height, const float* light, float* in_x, float* in_y, float* in_z,
+                               float* out_x, float* out_y, float* out_z, uint8_t* mask, void* stream)
+{
+  int rc = image_size(width, height);
+  if (rc) return rc;
+  if (!in_x || !in_y || !in_z || !out_x || !out_y || !out_z || !mask)
+    return fail(BBM_HIP_ERR_INVALID_ARG, "direction / mask pointer is NULL");
+  ImageArgs a;
+  std::memset(&a, 0, sizeof(a));
+  if ((rc = render_light(light, a.dir))) return rc;
+  a.op = kImageRender;
+  a.width = width; a.height = height; a.samples = 1;
+  a.ix = in_x; a.iy = in_y; a.iz = in_z; a.ox = out_x; a.oy = out_y; a.oz = out_z; a.mask = mask;
+  return sphere_dirs_launch(a, static_cast<hipStream_t>(stream));
+}
+
+int bbm_hip_render_shade(size_t npixels, const float* r, const float* g, const float* b, const float* in_z,
+                         const uint8_t* mask, float* image, void* stream)
+{
+  if (npixels == 0 || uint64_t(npixels) > kImageMaxPixels) return fail(BBM_HIP_ERR_INVALID_ARG, "pixel count must be in [1, 2^31]");
+  if (!r || !g || !b || !in_z || !mask) return fail(BBM_HIP_ERR_INVALID_ARG, "input pointer is NULL");
+  if (!image) return fail(BBM_HIP_ERR_INVALID_ARG, "image pointer is NULL");
+  return render_shade_launch(npixels, r, g, b, in_z, mask, image, static_cast<hipStream_t>(stream));
+}
+
+int bbm_hip_plot(int model_id, const float* params, int nparams, int kind, uint32_t width, uint32_t height,
+                 const float* view, uint64_t samples, float scale, int mask_zero, const float* xi0, const float* xi1,
+                 uint64_t seed, float* image, uint64_t* counts, void* stream)
+{
+  const CallExactScope mode_scope(model_id);
+  EvalArgs tmp;
+  const ModelEntry* e;
+  int rc = prepare(model_id, params, nparams, 0, tmp, e);
+  if (rc) return rc;
+  ImageArgs a;
+  std::memset(&a, 0, sizeof(a));
+  if ((rc = plot_args(kind, width, height, view, samples, scale, xi0, xi1, seed, a))) return rc;
+  if (!image) return fail(BBM_HIP_ERR_INVALID_ARG, "image pointer is NULL");
+  if (kind == kPlotSample && !counts) return fail(BBM_HIP_ERR_INVALID_ARG, "counts pointer is NULL");
+  a.mask_zero = mask_zero;
+  a.img = image;
+  a.counts = reinterpret_cast<unsigned long long*>(counts);
+  a.p = tmp.p;
+  const hipStream_t s = static_cast<hipStream_t>(stream);
+  if (kind == kPlotSample)
+  {
+    const hipError_t me = hipMemsetAsync(counts, 0, size_t(width) * height * sizeof(uint64_t), s);
+    if (me != hipSuccess) return fail(BBM_HIP_ERR_HIP, std::string("hipMemsetAsync: ") + hipGetErrorString(me));
+  }
+  return e->image(a, s);
+}
+
+int bbm_hip_plot_dirs(uint32_t width, uint32_t height, uint64_t samples, const float* xi0, const float* xi1, uint64_t seed,
+                      float* x, float* y, float* z, void* stream)
+{
+  const float view[3] = {0.0f, 0.0f, 1.0f};
+  ImageArgs a;
+  std::memset(&a, 0, sizeof(a));
+  int rc = plot_args(kPlotEval, width, height, view, samples, 1.0f, xi0, xi1, seed, a);
+  if (rc) return rc;
+  if (!x || !y || !z) return fail(BBM_HIP_ERR_INVALID_ARG, "direction pointer is NULL");
+  a.ix = x; a.iy = y; a.iz = z;
+  return plot_dirs_launch(a, static_cast<hipStream_t>(stream));
+}
+
+int bbm_hip_plot_accumulate(int kind, uint32_t width, uint32_t height, uint64_t samples, float scale, const float* xi0,
+                            const float* xi1, uint64_t seed, const float* r, const float* g, const float* b, float* image,
+                            void* stream)
+{
+  const float view[3] = {0.0f, 0.0f, 1.0f};
+  ImageArgs a;
+  std::memset(&a, 0, sizeof(a));
+  if (kind != kPlotEval && kind != kPlotPdf) return fail(BBM_HIP_ERR_INVALID_ARG, "unknown plot kind");
+  int rc = plot_args(kind, width, height, view, samples, scale, xi0, xi1, seed, a);
+  if (rc) return rc;
+  if (!r || (kind == kPlotEval && (!g || !b))) return fail(BBM_HIP_ERR_INVALID_ARG, "input pointer is NULL");
+  if (!image) return fail(BBM_HIP_ERR_INVALID_ARG, "image pointer is NULL");
+  a.img = image;
+  return plot_accumulate_launch(a, r, g, b, static_cast<hipStream_t>(stream));
+}
+
+int bbm_hip_plot_bin(uint32_t width, uint32_t height, size_t n, const float* dir_x, const float* dir_y, const float* dir_z,
+                     const float* pdf, int mask_zero, uint64_t* counts, void* stream)
+{
+  int rc = image_size(width, height);
+  if (rc) return rc;
+  if (!counts) return fail(BBM_HIP_ERR_INVALID_ARG, "counts pointer is NULL");
+  if (n > 0 && (!dir_x || !dir_y || !dir_z || !pdf)) return fail(BBM_HIP_ERR_INVALID_ARG, "direction / pdf pointer is NULL");
+  const hipStream_t s = static_cast<hipStream_t>(stream);
+  const hipError_t me = hipMemsetAsync(counts, 0, size_t(width) * height * sizeof(uint64_t), s);
+  if (me != hipSuccess) return fail(BBM_HIP_ERR_HIP, std::string("hipMemsetAsync: ") + hipGetErrorString(me));
+  if (n == 0) return BBM_HIP_OK;
+  return plot_bin_launch(width, height, n, dir_x, dir_y, dir_z, pdf, mask_zero, reinterpret_cast<unsigned long long*>(counts), s);
+}
+
+int bbm_hip_plot_counts_image(const uint64_t* counts, uint32_t width, uint32_t height, uint64_t samples, float scale,
+                              float* image, void* stream)
+{
+  int rc = image_size(width, height);
+  if (rc) return rc;
+  if (samples == 0) return fail(BBM_HIP_ERR_INVALID_ARG, "samples must be positive");
+  if (!counts) return fail(BBM_HIP_ERR_INVALID_ARG, "counts pointer is NULL");
+  if (!image) return fail(BBM_HIP_ERR_INVALID_ARG, "image pointer is NULL");
+  return count_image_launch(reinterpret_cast<const unsigned long long*>(counts), width, height, samples, scale, image,
+                            static_cast<hipStream_t>(stream));
+}
+
+int bbm_hip_plot_draws(uint64_t seed, uint64_t offset, size_t n, float* xi0, float* xi1, void* stream)
+{
+  if (n == 0) return BBM_HIP_OK;
+  if (!xi0 || !xi1) return fail(BBM_HIP_ERR_INVALID_ARG, "xi pointer is NULL");
+  return plot_draws_launch(seed, offset, n, xi0, xi1, static_cast<hipStream_t>(stream));
 }
 
 int bbm_hip_check_draws(int test, uint64_t seed, int slot, int draw, uint64_t offset, size_t n,

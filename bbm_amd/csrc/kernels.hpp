@@ -1306,9 +1306,11 @@ int launch_loss(const LossArgs& a0, hipStream_t s)
 }  // namespace bbmhip
 
 #include "check.hpp"
+#include "image.hpp"
 
 namespace bbmhip {
 
+using ImageLauncher = int (*)(const ImageArgs&, hipStream_t);
 using LossLauncher = int (*)(const LossArgs&, hipStream_t);
 using CheckLauncher = int (*)(int, const CheckArgs&, double*, hipStream_t);
 using EvalLauncher = int (*)(const EvalArgs&, int, hipStream_t);

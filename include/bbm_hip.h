@@ -517,6 +517,61 @@ int bbm_hip_check_trials(int test, uint64_t seed, int ntrials, int sphere, float
 int bbm_hip_sphere_dirs(const float* xi0, const float* xi1, size_t n, int hemisphere, float* x, float* y, float* z,
                         void* stream);
 
+/* ---------------------------------------------------------------- image tools (renderSphere, plotBsdf) */
+
+/* bin/renderSphere.cpp and bin/plotBsdf.cpp as image-space kernels, floatRGB.  Images are (3, height, width) float
+ * planes in device memory, row y = 0 first (io/pfm.h writes them bottom-up).  A fused aggregate's id takes
+ * BBM_HIP_RUNTIME_AGGREGATE (the tools build their BSDF with bsdf_import) and the BBM_HIP_CALL_* flags as
+ * everywhere else.  Bad arguments (zero width / height, more than 2^31 pixels, a NULL image, a zero or non-finite
+ * light / view, samples == 0, an unknown kind) return BBM_HIP_ERR_INVALID_ARG before anything is launched.
+ *
+ * bbm_hip_render_sphere: pixel = eval(in, out) * |z(in)| on the sphere's normal map lit from `light` (3 host
+ * floats, any length; the tool's default is (0, 0, -1)) and seen along (0, 0, -1); 0 off the sphere.  in_* / out_*
+ * (width * height floats each) and mask (width * height bytes) also receive each pixel's local directions and
+ * whether it is shaded; each group may be NULL. */
+int bbm_hip_render_sphere(int model_id, const float* params, int nparams, uint32_t width, uint32_t height,
+                          const float* light, float* image, float* in_x, float* in_y, float* in_z,
+                          float* out_x, float* out_y, float* out_z, uint8_t* mask, void* stream);
+
+#define BBM_HIP_PLOT_EVAL 0     /* plot=eval: mean of eval(light, view) cosTheta(light) over the pixel's samples */
+#define BBM_HIP_PLOT_PDF 1      /* plot=pdf: mean of pdf(light, view) times the pixel's solid angle */
+#define BBM_HIP_PLOT_SAMPLE 2   /* plot=sample: histogram of width * height * samples draws of sample(view, xi) */
+
+/* bbm_hip_plot: a (phi, theta) slice of the model for one `view` (3 host floats, normalised here).  Pixel (x, y),
+ * sample s uses draw g = (y * width + x) * samples + s: (u_phi, u_theta) = (xi0[g], xi1[g]) when the caller passes
+ * its own uniforms (device, width * height * samples floats each), else the library's counter-based generator on
+ * `seed` (bbm_hip_plot_draws returns the same numbers).  SAMPLE takes draw g for its g-th sample, counts bins with
+ * integer atomics into counts (device, width * height; required for SAMPLE, zeroed here) and replays the
+ * reference's float accumulation per bin from its count; mask_zero skips draws whose pdf <= epsilon.  The finished
+ * image is multiplied by scale. */
+int bbm_hip_plot(int model_id, const float* params, int nparams, int kind, uint32_t width, uint32_t height,
+                 const float* view, uint64_t samples, float scale, int mask_zero, const float* xi0, const float* xi1,
+                 uint64_t seed, float* image, uint64_t* counts, void* stream);
+
+/* The uniforms bbm_hip_plot draws for draws offset .. offset + n - 1 of `seed`. */
+int bbm_hip_plot_draws(uint64_t seed, uint64_t offset, size_t n, float* xi0, float* xi1, void* stream);
+
+/* The staged path, for models without a fused image kernel (composed aggregates and runtime trees, whose eval / pdf /
+ * sample run through bbm_hip_aggregate_*): the same directions, weights and summation order as the fused kernels,
+ * so a model that has both gets the same image bit for bit.
+ *   render: bbm_hip_render_sphere_dirs -> eval(in, out) with the mask -> bbm_hip_render_shade
+ *   eval / pdf: bbm_hip_plot_dirs (one light direction per draw) -> eval / pdf(light, view) -> bbm_hip_plot_accumulate
+ *     (r, g, b: the values per draw; PDF reads r only)
+ *   sample: sample(view, draws) -> bbm_hip_plot_bin (counts, zeroed here) -> bbm_hip_plot_counts_image */
+int bbm_hip_render_sphere_dirs(uint32_t width, uint32_t height, const float* light, float* in_x, float* in_y, float* in_z,
+                               float* out_x, float* out_y, float* out_z, uint8_t* mask, void* stream);
+int bbm_hip_render_shade(size_t npixels, const float* r, const float* g, const float* b, const float* in_z,
+                         const uint8_t* mask, float* image, void* stream);
+int bbm_hip_plot_dirs(uint32_t width, uint32_t height, uint64_t samples, const float* xi0, const float* xi1, uint64_t seed,
+                      float* x, float* y, float* z, void* stream);
+int bbm_hip_plot_accumulate(int kind, uint32_t width, uint32_t height, uint64_t samples, float scale, const float* xi0,
+                            const float* xi1, uint64_t seed, const float* r, const float* g, const float* b, float* image,
+                            void* stream);
+int bbm_hip_plot_bin(uint32_t width, uint32_t height, size_t n, const float* dir_x, const float* dir_y, const float* dir_z,
+                     const float* pdf, int mask_zero, uint64_t* counts, void* stream);
+int bbm_hip_plot_counts_image(const uint64_t* counts, uint32_t width, uint32_t height, uint64_t samples, float scale,
+                              float* image, void* stream);
+
 /* ---------------------------------------------------------------- device math verification */
 
 /* The device restatements of the host libm float functions the reference's native backbone calls (glibc 2.35's
