@@ -185,12 +185,6 @@ struct Scratch
   }
 };
 
-int launched()
-{
-  const hipError_t e = hipGetLastError();
-  return (e == hipSuccess) ? BBM_HIP_OK : fail(BBM_HIP_ERR_HIP, std::string("kernel launch failed: ") + hipGetErrorString(e));
-}
-
 // ------------------------------------------------------------------ leaves: the single-model entry points
 template<class T> struct Leaf;
 

@@ -1,16 +1,13 @@
-// bbm_amd/csrc/f64.hip -- doubleRGB kernels (f64.hpp) and their registry by model name.
+// bbm_amd/csrc/f64.hip -- doubleRGB kernels (f64.hpp) and their launchers, exported per floatRGB composition
+// (f64_launchers_of, f64_args.hpp) for the registry (registry.hip).
 #include <hip/hip_runtime.h>
-#include <cstring>
 #include <string>
 
 #include "../../include/bbm_hip.h"
 #include "f64.hpp"
+#include "models.hpp"     // the floatRGB compositions, as keys only
 
 namespace bbmhip {
-
-int fail(int code, const std::string& msg);
-std::string scratch_failure();
-
 namespace f64 {
 namespace {
 
@@ -108,12 +105,6 @@ unsigned grid(uint64_t units)
 }
 
 bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-
-int launched(const char* what)
-{
-  const hipError_t e = hipGetLastError();
-  return (e == hipSuccess) ? 0 : fail(BBM_HIP_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
-}
 
 // Grid cap (0 = full grid): the Student-T NDF's per-thread setup (two f64 tgamma and a pow) is amortised over
 // several grid-stride iterations (the floatRGB kernels' eval_grid_cap, kernels.hpp)
@@ -259,78 +250,28 @@ int launch_sample(const SampleArgsF64& a0, hipStream_t s)
   return launched("k_sample_f64");
 }
 
-struct Entry { const char* name; F64Launchers l; };
-#define BBM_HIP_F64(NAME, M) {NAME, {&launch_eval_pdf<M>, &launch_reflectance<M>, &launch_sample<M>}}
-// names as in the floatRGB registry (bbm_hip.hip); aliases share a composition as they do there
-const Entry kF64[] = {
-  BBM_HIP_F64("Lambertian", Lambertian),
-  BBM_HIP_F64("OrenNayar", OrenNayar),
-  BBM_HIP_F64("CookTorrance", CookTorranceM),
-  BBM_HIP_F64("LowCookTorrance", CookTorranceM),   // bsdfmodel/low.h:32-33
-  BBM_HIP_F64("GGX", GGXM),
-  BBM_HIP_F64("CookTorranceWalter", CookTorranceWalterM),
-  BBM_HIP_F64("CookTorranceHeitz", CookTorranceHeitzM),
-  BBM_HIP_F64("GGXHeitz", GGXHeitzM),
-  BBM_HIP_F64("NganCookTorrance", NganCookTorranceM),
-  BBM_HIP_F64("PhongWalter", PhongWalterM),
-  BBM_HIP_F64("Ribardiere", RibardiereM),
-  BBM_HIP_F64("RibardiereAnisotropic", RibardiereAnisoM),
-  BBM_HIP_F64("LowMicrofacet", LowMicrofacetM),
-  BBM_HIP_F64("LowMicrofacetFit", LowMicrofacetM),
-  BBM_HIP_F64("Aggregate<Lambertian,CookTorrance>", AggCookTorranceM),
-  BBM_HIP_F64("Aggregate<Lambertian,LowCookTorrance>", AggCookTorranceM),
-  BBM_HIP_F64("Aggregate<Lambertian,GGX>", AggGGXM),
-  BBM_HIP_F64("Aggregate<Lambertian,NganCookTorrance>", AggNganCookTorranceM),
-  BBM_HIP_F64("Aggregate<Lambertian,LowMicrofacetFit>", AggLowMicrofacetM),
-  BBM_HIP_F64("Ward", WardM),
-  BBM_HIP_F64("WardDuer", WardDuerM),
-  BBM_HIP_F64("WardDuerGeislerMoroder", WardDGMM),
-  BBM_HIP_F64("NganWard", NganWardM),
-  BBM_HIP_F64("NganWardDuer", NganWardDuerM),
-  BBM_HIP_F64("Phong", PhongLobe),
-  BBM_HIP_F64("NganBlinnPhong", PhongLobe),   // ngan.h:43-44
-  BBM_HIP_F64("Lafortune", LafortuneM),
-  BBM_HIP_F64("NganLafortune", NganLafortuneM),
-  BBM_HIP_F64("AshikhminShirley", ASM),
-  BBM_HIP_F64("AshikhminShirleyFull", ASFullM),
-  BBM_HIP_F64("LowAshikhminShirley", LowASM),
-  BBM_HIP_F64("NganAshikhminShirley", NganASM),
-  BBM_HIP_F64("LowSmooth", LowSmooth),
-  BBM_HIP_F64("Aggregate<Lambertian,LowAshikhminShirley>", AggLowASM),
-  BBM_HIP_F64("Aggregate<Lambertian,LowSmooth>", AggLowSmoothM),
-  BBM_HIP_F64("Aggregate<Lambertian,NganAshikhminShirley>", AggNganASM),
-  BBM_HIP_F64("Aggregate<Lambertian,NganBlinnPhong>", AggPhongM),
-  BBM_HIP_F64("Aggregate<Lambertian,NganLafortune>", AggNganLafortuneM),
-  BBM_HIP_F64("Aggregate<Lambertian,NganWard>", AggNganWardM),
-  BBM_HIP_F64("Aggregate<Lambertian,NganWardDuer>", AggNganWardDuerM),
-  BBM_HIP_F64("Bagher", Bagher),
-  BBM_HIP_F64("Aggregate<Lambertian,Bagher>", AggBagherM),
-  BBM_HIP_F64("EPD", EpdM),
-  BBM_HIP_F64("He", HeM),
-  BBM_HIP_F64("HeWestin", HeWestinM),
-  BBM_HIP_F64("HeHolzschuch", HeHolzschuchM),
-  BBM_HIP_F64("NganHe", NganHeM),
-  BBM_HIP_F64("Aggregate<Lambertian,NganHe>", AggNganHeM),
-};
-#undef BBM_HIP_F64
-
-static_assert(Lambertian::kParams == 3 && OrenNayar::kParams == 4 && CookTorranceM::kParams == 5 && GGXM::kParams == 5 &&
-              CookTorranceHeitzM::kParams == 6 && GGXHeitzM::kParams == 6 && NganCookTorranceM::kParams == 5 &&
-              PhongWalterM::kParams == 5 && RibardiereM::kParams == 6 && RibardiereAnisoM::kParams == 7 &&
-              LowMicrofacetM::kParams == 6 && AggCookTorranceM::kParams == 8 && WardM::kParams == 5 &&
-              NganWardM::kParams == 4 && PhongLobe::kParams == 4 && LafortuneM::kParams == 7 &&
-              NganLafortuneM::kParams == 6 && ASM::kParams == 5 && ASFullM::kParams == 8 && LowASM::kParams == 5 &&
-              NganASM::kParams == 5 && LowSmooth::kParams == 6 && Bagher::kParams == 30 && EpdM::kParams == 4 && HeM::kParams == 8 && NganHeM::kParams == 6, "f64 nparams must match the floatRGB registry");
+// a floatRGB composition's doubleRGB restatement: the alias of the same name in this namespace (f64.hpp)
+template<class F> struct double_of;
 
 }  // namespace
 
-const F64Launchers* f64_launchers(const char* name)
+template<class F> F64Launchers f64_launchers_of()
 {
-  if (!name) return nullptr;
-  for (const auto& e : kF64)
-    if (std::strcmp(e.name, name) == 0) return &e.l;
-  return nullptr;
+  using M = typename double_of<F>::type;
+  return {&launch_eval_pdf<M>, &launch_reflectance<M>, &launch_sample<M>};
 }
+
+#define BBM_HIP_F64(M)                                                          \
+  namespace { template<> struct double_of<::bbmhip::M> { using type = M; }; }   \
+  template F64Launchers f64_launchers_of<::bbmhip::M>();
+BBM_HIP_DIFFUSE_MODELS(BBM_HIP_F64)
+BBM_HIP_MICROFACET_MODELS(BBM_HIP_F64)
+BBM_HIP_LOBE_MODELS(BBM_HIP_F64)
+BBM_HIP_SPECTRAL_MODELS(BBM_HIP_F64)
+BBM_HIP_EPD_MODELS(BBM_HIP_F64)
+BBM_HIP_HE_MODELS(BBM_HIP_F64)
+BBM_HIP_AGGREGATE_MODELS(BBM_HIP_F64)
+#undef BBM_HIP_F64
 
 }  // namespace f64
 }  // namespace bbmhip

@@ -15,6 +15,7 @@
 #pragma once
 #include "math.hpp"
 #include "epd.hpp"      // gamma_q_inv_d
+#include "f64_args.hpp"
 
 // Round-3 defaults, each with an A/B switch back (tools/build_variant_units.sh), measured per 10 M pairs in
 // tools/gpu_r03_u.sh (profiles/r03_f64_fdiv_ab.txt):
@@ -35,8 +36,6 @@
 
 namespace bbmhip {
 namespace f64 {
-
-constexpr int kMaxParamsF64 = 64;      // parameter block size; the last slot carries the aggregate mode (Aggregate)
 
 constexpr double kEps = 2.220446049250313080847263336181640625e-16;   // numeric_limits<double>::epsilon()
 constexpr double kPi = 3.141592653589793115997963468544185161590576171875;          // std::numbers::pi (double)
@@ -1646,53 +1645,9 @@ using AggNganHeM = Aggregate<Lambertian, NganHeM>;
 
 // ------------------------------------------------------------------------------------------------- kernels
 
-struct ParamBlockF64 { double v[kMaxParamsF64]; };
-
-struct EvalArgsF64
-{
-  const double* ix; const double* iy; const double* iz;
-  const double* ox; const double* oy; const double* oz;
-  const uint8_t* mask;
-  double* r; double* g; double* b; double* pdf;
-  uint64_t n;
-  uint32_t component;
-  ParamBlockF64 p;
-};
-
-struct ReflArgsF64
-{
-  const double* ox; const double* oy; const double* oz;
-  const uint8_t* mask;
-  double* r; double* g; double* b;
-  uint64_t n;
-  uint32_t component;
-  ParamBlockF64 p;
-};
-
-struct SampleArgsF64
-{
-  const double* ox; const double* oy; const double* oz;
-  const double* xi0; const double* xi1;
-  const uint8_t* mask;
-  double* dx; double* dy; double* dz; double* pdf; uint32_t* flag;
-  uint64_t n;
-  uint32_t component;
-  ParamBlockF64 p;
-};
-
-using EvalLauncherF64 = int (*)(const EvalArgsF64&, hipStream_t);
-using ReflLauncherF64 = int (*)(const ReflArgsF64&, hipStream_t);
-using SampleLauncherF64 = int (*)(const SampleArgsF64&, hipStream_t);
-
-// A composition's f64 launchers (f64.hip), looked up by registry name; nullptr for a model without a doubleRGB
-// kernel.
-struct F64Launchers { EvalLauncherF64 eval_pdf; ReflLauncherF64 reflectance; SampleLauncherF64 sample; };
+// ParamBlockF64, the argument structs and the launcher bundle: f64_args.hpp
 
 }  // namespace f64
 // EPD's shadowing table on the current device, built on first use (inst_epd.hip); nullptr on failure
 const float* epd_table_device(hipStream_t s);
-namespace f64 {
-const F64Launchers* f64_launchers(const char* name);
-
-}  // namespace f64
 }  // namespace bbmhip

@@ -133,13 +133,6 @@ __global__ __launch_bounds__(kBlock) void k_plot_bin(uint32_t w, uint32_t h, uin
     }
 }
 
-int launched(const char* what)
-{
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(BBM_HIP_ERR_HIP, std::string(what) + ": kernel launch failed: " + hipGetErrorString(e));
-  return BBM_HIP_OK;
-}
-
 unsigned pixel_blocks(uint64_t npix) { return unsigned((npix + kBlock - 1) / kBlock); }
 unsigned draw_blocks(uint64_t n)
 {
@@ -156,32 +149,32 @@ int count_image_launch(const unsigned long long* counts, uint32_t width, uint32_
   const uint64_t npix = uint64_t(width) * height;
   const double addend = 1.0 / double(float(npix * samples));      // 1.0 / (float)(width * height * samples)
   hipLaunchKernelGGL(k_count_image, dim3(pixel_blocks(npix)), dim3(kBlock), 0, s, counts, npix, addend, scale, img);
-  return launched("count replay");
+  return launched("count replay: kernel launch failed");
 }
 
 int plot_draws_launch(uint64_t seed, uint64_t offset, uint64_t n, float* xi0, float* xi1, hipStream_t s)
 {
   hipLaunchKernelGGL(k_plot_draws, dim3(draw_blocks(n)), dim3(kBlock), 0, s, plot_key(seed), offset, n, xi0, xi1);
-  return launched("plot draws");
+  return launched("plot draws: kernel launch failed");
 }
 
 int sphere_dirs_launch(const ImageArgs& a, hipStream_t s)
 {
   hipLaunchKernelGGL(k_sphere_pixel_dirs, dim3(pixel_blocks(uint64_t(a.width) * a.height)), dim3(kBlock), 0, s, a);
-  return launched("sphere directions");
+  return launched("sphere directions: kernel launch failed");
 }
 
 int render_shade_launch(uint64_t npix, const float* r, const float* g, const float* b, const float* iz, const uint8_t* mask,
                         float* img, hipStream_t s)
 {
   hipLaunchKernelGGL(k_render_shade, dim3(pixel_blocks(npix)), dim3(kBlock), 0, s, npix, r, g, b, iz, mask, img);
-  return launched("render shade");
+  return launched("render shade: kernel launch failed");
 }
 
 int plot_dirs_launch(const ImageArgs& a, hipStream_t s)
 {
   hipLaunchKernelGGL(k_plot_light_dirs, dim3(draw_blocks(uint64_t(a.width) * a.height * a.samples)), dim3(kBlock), 0, s, a);
-  return launched("plot directions");
+  return launched("plot directions: kernel launch failed");
 }
 
 int plot_accumulate_launch(const ImageArgs& a, const float* r, const float* g, const float* b, hipStream_t s)
@@ -189,14 +182,14 @@ int plot_accumulate_launch(const ImageArgs& a, const float* r, const float* g, c
   const dim3 grid(pixel_blocks(uint64_t(a.width) * a.height));
   if (a.op == kPlotEval) hipLaunchKernelGGL((k_plot_accumulate<kPlotEval>), grid, dim3(kBlock), 0, s, a, r, g, b);
   else hipLaunchKernelGGL((k_plot_accumulate<kPlotPdf>), grid, dim3(kBlock), 0, s, a, r, g, b);
-  return launched("plot accumulate");
+  return launched("plot accumulate: kernel launch failed");
 }
 
 int plot_bin_launch(uint32_t w, uint32_t h, uint64_t n, const float* dx, const float* dy, const float* dz, const float* pdf,
                     int mask_zero, unsigned long long* counts, hipStream_t s)
 {
   hipLaunchKernelGGL(k_plot_bin, dim3(draw_blocks(n)), dim3(kBlock), 0, s, w, h, n, dx, dy, dz, pdf, mask_zero, counts);
-  return launched("plot bin");
+  return launched("plot bin: kernel launch failed");
 }
 
 }  // namespace bbmhip

@@ -1,7 +1,7 @@
 // bbm_amd/csrc/kernels.hpp -- the streaming kernels and their host-side launchers, templated on
 // the model composition.  Included by the per-family instantiation units (inst_*.hip), which
 // explicitly instantiate launch_eval_pdf<M> / launch_sample<M> for their models, and by the
-// registry unit (bbm_hip.hip), which only takes their addresses (extern template).
+// registry unit (registry.hip), which only takes their addresses (extern template).
 //
 // Layout and launch: directions are SoA float32 in HBM; one thread owns four
 // consecutive pairs, so each lane issues one 16-byte load per input array and one 16-byte store
@@ -18,6 +18,7 @@
 #include <string>
 
 #include "../../include/bbm_hip.h"
+#include "host.hpp"
 #include "math.hpp"
 #include "microfacet.hpp"
 #include "fit.hpp"
@@ -27,19 +28,6 @@ namespace bbmhip {
 constexpr int kMaxParams = 64;
 constexpr int kBlock = 256;
 constexpr int kMaxBlocks = 1 << 22;   // effectively one workgroup per 1024 pairs (full grid)
-
-// Record `msg` as the calling thread's last error (bbm_hip_last_error) and return `code`.
-int fail(int code, const std::string& msg);
-
-// Stream-ordered device scratch (bbm_hip.hip): per-launch derived data (the tabulated samplers' CDFs) and the
-// composed aggregates' per-lane temporaries.  A released block keeps an event recorded on the releasing
-// stream; re-acquiring it on the same stream needs nothing (stream order), on another stream that stream
-// waits for the event on the GPU.  No host synchronisation; blocks are kept for reuse.  (Replaces
-// hipMallocAsync / hipFreeAsync on the caller's stream, under which tests/cpp/adapter_check -- a plain C++
-// host program on the null stream -- saw He CDFs and composed-aggregate outputs corrupted at random.)
-void* scratch_acquire(size_t bytes, hipStream_t s);
-std::string scratch_failure();   // why the calling thread's last scratch_acquire returned nullptr
-void scratch_release(void* p, hipStream_t s);
 
 struct ParamBlock { float v[kMaxParams]; };
 
@@ -1316,5 +1304,20 @@ using CheckLauncher = int (*)(int, const CheckArgs&, double*, hipStream_t);
 using EvalLauncher = int (*)(const EvalArgs&, int, hipStream_t);
 using SampleLauncher = int (*)(const SampleArgs&, hipStream_t);
 using ReflLauncher = int (*)(const ReflArgs&, hipStream_t);
+
+// A composition's launchers: what a registry row (registry.hip) holds of its kernels.
+struct Launchers
+{
+  EvalLauncher eval_pdf;
+  SampleLauncher sample;
+  ReflLauncher reflectance;
+  LossLauncher loss;
+  CheckLauncher check;
+  ImageLauncher image;
+};
+template<class M> constexpr Launchers launchers()
+{
+  return {&launch_eval_pdf<M>, &launch_sample<M>, &launch_reflectance<M>, &launch_loss<M>, &launch_check<M>, &launch_image<M>};
+}
 
 }  // namespace bbmhip

@@ -19,58 +19,10 @@
 #include <vector>
 
 #include "../../include/bbm_hip.h"
+#include "host.hpp"
 
 namespace bbmhip {
-int fail(int code, const std::string& msg);
-
 namespace {
-
-// attribute layouts in declaration order (bbm::reflection::attributes, the order toString prints and
-// parameter_values packs), "name:count" with count = product of the attribute's shape
-struct Layout { const char* model; const char* attrs; };
-const Layout kLayouts[] = {
-  {"Lambertian", "albedo:3"},
-  {"OrenNayar", "albedo:3,roughness:1"},
-  {"CookTorrance", "albedo:3,roughness:1,eta:1"},
-  {"CookTorranceHeitz", "albedo:3,roughness:2,eta:1"},
-  {"CookTorranceWalter", "albedo:3,roughness:1,eta:1"},
-  {"GGX", "albedo:3,roughness:1,eta:1"},
-  {"GGXHeitz", "albedo:3,roughness:2,eta:1"},
-  {"PhongWalter", "albedo:3,sharpness:1,eta:1"},
-  {"Ribardiere", "albedo:3,roughness:1,gamma:1,eta:1"},
-  {"RibardiereAnisotropic", "albedo:3,roughness:2,gamma:1,eta:1"},
-  {"Bagher", "albedo:3,K:3,Lambda:3,c:3,theta0:3,k:3,alpha:3,p:3,eta:6"},
-  {"LowCookTorrance", "albedo:3,roughness:1,eta:1"},
-  {"LowMicrofacet", "A:3,B:1,C:1,eta:1"},
-  {"LowMicrofacetFit", "A:3,B:1,C:1,eta:1"},
-  {"NganCookTorrance", "albedo:3,roughness:1,eta:1"},
-  {"Ward", "albedo:3,roughness:2"},
-  {"WardDuer", "albedo:3,roughness:2"},
-  {"WardDuerGeislerMoroder", "albedo:3,roughness:2"},
-  {"NganWard", "albedo:3,roughness:1"},
-  {"NganWardDuer", "albedo:3,roughness:1"},
-  {"Phong", "albedo:3,sharpness:1"},
-  {"NganBlinnPhong", "albedo:3,sharpness:1"},
-  {"Lafortune", "albedo:3,Cxy:2,Cz:1,sharpness:1"},
-  {"NganLafortune", "albedo:3,Cxy:1,Cz:1,sharpness:1"},
-  {"AshikhminShirley", "fresnelReflectance:3,sharpness:2"},
-  {"AshikhminShirleyFull", "diffuseReflectance:3,fresnelReflectance:3,sharpness:2"},
-  {"LowAshikhminShirley", "albedo:3,fresnelReflectance:1,sharpness:1"},
-  {"NganAshikhminShirley", "albedo:3,fresnelReflectance:1,sharpness:1"},
-  {"LowSmooth", "A:3,B:1,C:1,eta:1"},
-  {"EPD", "beta:1,p:1,eta:2"},
-  {"He", "roughness:1,autocorrelation:1,eta:6"},
-  {"HeWestin", "roughness:1,autocorrelation:1,eta:6"},
-  {"HeHolzschuch", "roughness:1,autocorrelation:1,eta:6"},
-  {"NganHe", "albedo:3,roughness:1,autocorrelation:1,eta:1"},
-};
-
-const char* layout_of(const std::string& model)
-{
-  for (const auto& l : kLayouts)
-    if (model == l.model) return l.attrs;
-  return nullptr;
-}
 
 struct Attr { std::string name; int count; };
 
@@ -135,9 +87,9 @@ struct Child { std::string name; std::vector<float> params; };
 // Name(attr = v, ...) with the defaults of the registry entry filled in first
 bool parse_single(Parser& p, const std::string& name, Child& out, int& code)
 {
-  const char* lay = layout_of(name);
-  const int id = lay ? bbm_hip_model_id(name.c_str()) : -1;
-  if (!lay || id < 0) { code = BBM_HIP_ERR_INVALID_MODEL; p.err = "unknown BSDF model: " + name; return false; }
+  const int id = bbm_hip_model_id(name.c_str());
+  const char* lay = id >= 0 ? bbm_hip_model_layout(id) : nullptr;     // nullptr: no attributes to set from a string
+  if (!lay) { code = BBM_HIP_ERR_INVALID_MODEL; p.err = "unknown BSDF model: " + name; return false; }
   const std::vector<Attr> attrs = split_layout(lay);
   const int np = bbm_hip_model_nparams(id);
   out.name = name;
@@ -266,13 +218,6 @@ bool parse_root(const std::string& s, Node& root, int& rc)
 using namespace bbmhip;
 
 extern "C" {
-
-const char* bbm_hip_model_layout(int model_id)
-{
-  const char* name = bbm_hip_model_name(model_id);
-  if (!name) { fail(BBM_HIP_ERR_INVALID_MODEL, "unknown model id " + std::to_string(model_id)); return nullptr; }
-  return layout_of(name);
-}
 
 int bbm_hip_parse_model(const char* str, int* model_ids, float* params, int* nparams, int max_children,
                         int params_capacity)

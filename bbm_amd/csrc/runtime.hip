@@ -18,13 +18,7 @@
 #include <vector>
 
 #include "../../include/bbm_hip.h"
-
-namespace bbmhip {
-int fail(int code, const std::string& msg);
-std::string scratch_failure();
-void* scratch_acquire(size_t bytes, hipStream_t s);
-void scratch_release(void* p, hipStream_t s);
-}  // namespace bbmhip
+#include "host.hpp"
 
 using namespace bbmhip;
 

@@ -47,9 +47,51 @@ def test_abi_version(lib):
     assert lib.bbm_hip_abi_version() == 12
 
 
+# Model ids are indices into the registry and cross the ABI: the 35 single models, then the 14 fused aggregates.
+REGISTRY_ORDER = [
+    "Lambertian", "CookTorrance", "LowCookTorrance", "GGX", "CookTorranceWalter", "CookTorranceHeitz", "GGXHeitz",
+    "NganCookTorrance", "PhongWalter", "Ribardiere", "RibardiereAnisotropic", "OrenNayar", "LowMicrofacet",
+    "LowMicrofacetFit", "Ward", "WardDuer", "WardDuerGeislerMoroder", "NganWard", "NganWardDuer", "Phong",
+    "NganBlinnPhong", "Lafortune", "NganLafortune", "AshikhminShirley", "AshikhminShirleyFull", "LowAshikhminShirley",
+    "NganAshikhminShirley", "LowSmooth", "Bagher", "EPD", "He", "HeWestin", "HeHolzschuch", "NganHe", "Merl",
+    "Aggregate<Lambertian,Bagher>", "Aggregate<Lambertian,CookTorrance>", "Aggregate<Lambertian,GGX>",
+    "Aggregate<Lambertian,LowCookTorrance>", "Aggregate<Lambertian,LowAshikhminShirley>",
+    "Aggregate<Lambertian,LowMicrofacetFit>", "Aggregate<Lambertian,LowSmooth>",
+    "Aggregate<Lambertian,NganAshikhminShirley>", "Aggregate<Lambertian,NganBlinnPhong>",
+    "Aggregate<Lambertian,NganCookTorrance>", "Aggregate<Lambertian,NganLafortune>", "Aggregate<Lambertian,NganWard>",
+    "Aggregate<Lambertian,NganWardDuer>", "Aggregate<Lambertian,NganHe>",
+]
+
+
+def test_registry_order_is_stable(lib):
+    assert len(REGISTRY_ORDER) == 49 and lib.bbm_hip_num_models() == 49
+    for i, name in enumerate(REGISTRY_ORDER):
+        assert lib.bbm_hip_model_name(i).decode() == name, i
+        assert lib.bbm_hip_model_id(name.encode()) == i, name
+
+
+def test_layout_null_for_merl_and_aggregates(lib):
+    """Merl and the fused aggregates have no attribute layout of their own; an unknown id is an error."""
+    from bbm_amd import _lib
+    assert lib.bbm_hip_model_layout(REGISTRY_ORDER.index("Merl")) is None
+    aggregates = [i for i, name in enumerate(REGISTRY_ORDER) if name.startswith("Aggregate<")]
+    assert len(aggregates) == 14
+    for i in aggregates:
+        assert lib.bbm_hip_model_layout(i) is None, REGISTRY_ORDER[i]
+        assert lib.bbm_hip_model_layout(i | _lib.RUNTIME_AGGREGATE) is None, REGISTRY_ORDER[i]
+    assert lib.bbm_hip_model_layout(REGISTRY_ORDER.index("CookTorrance")) == b"albedo:3,roughness:1,eta:1"
+    assert lib.bbm_hip_model_layout(12_345) is None
+    assert b"12345" in lib.bbm_hip_last_error()
+
+
 def test_f64_registry(lib):
-    """doubleRGB kernels: the microfacet family, the diffuse models and their Aggregate(Lambertian, X) fits."""
+    """doubleRGB kernels: every analytic model and every Aggregate(Lambertian, X) fit; not the measured Merl."""
+    from bbm_amd import _lib
     has = {lib.bbm_hip_model_name(i).decode(): lib.bbm_hip_model_has_f64(i) for i in range(lib.bbm_hip_num_models())}
+    assert has == {name: int(name != "Merl") for name in REGISTRY_ORDER}
+    for i, name in enumerate(REGISTRY_ORDER):
+        if name.startswith("Aggregate<"):
+            assert lib.bbm_hip_model_has_f64(i | _lib.RUNTIME_AGGREGATE) == has[name], name
     for name in ("Lambertian", "OrenNayar", "CookTorrance", "GGX", "CookTorranceHeitz", "Ribardiere",
                  "LowMicrofacetFit", "Aggregate<Lambertian,CookTorrance>", "Aggregate<Lambertian,NganCookTorrance>"):
         assert has[name] == 1, name

@@ -124,7 +124,7 @@ def test_composed_equals_fused_for_the_fits_form(bbm):
 
 
 def test_scratch_reuse_across_streams(bbm):
-    """The stream-ordered scratch pool (bbm_hip.hip scratch_acquire / scratch_release): composed aggregates and
+    """The stream-ordered scratch pool (scratch.hip scratch_acquire / scratch_release): composed aggregates and
     He CDFs issued alternately on two streams, without host synchronisation between them, give exactly the
     results of the same calls issued one at a time (a block released on one stream and re-acquired on the other
     is waited for on the GPU)."""
