@@ -94,6 +94,7 @@ def plot(model, kind, width=512, height=256, view=(0, 0, 1), samples=1, scale=1.
         if not np.all(np.isfinite(v)):
             raise _lib.BackboneError(_lib.ERR_INVALID_ARG, "view must be a finite non-zero vector")
         vd = torch.from_numpy(np.repeat(v.astype(np.float32)[:, None], n, axis=1)).to(dev)
+        _on_stream(stream, vd)
         if kind == "sample":
             u = xi if xi is not None else plot_draws(seed, 0, n, stream)
             smp = model.sample(vd, u, stream=stream)

@@ -68,7 +68,8 @@ def render_sphere(model, width=512, height=512, light=(0, 0, -1), *, return_dirs
                                              lvec, img.data_ptr(), *ptrs(din), *ptrs(dout),
                                              None if mask is None else mask.data_ptr(), s))
     if return_dirs:
-        return img, din.view(3, height, width), dout.view(3, height, width), mask.view(height, width).bool()
+        # the mask's bytes are 0 / 1: reinterpreted, not converted (a conversion would run on the current stream)
+        return img, din.view(3, height, width), dout.view(3, height, width), mask.view(height, width).view(torch.bool)
     return img
 
 

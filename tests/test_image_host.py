@@ -140,6 +140,81 @@ def test_count_replay_is_not_a_product():
     assert diff > 0
 
 
+def replay_binades(count, ndraws):
+    """The same float as replay(count, ndraws), a whole binade at a time -> (value, additions that moved it).
+
+    While v = m u lies in [2^e, 2^(e+1)) (u = 2^(e-23), the float spacing) and v + a stays below 2^(e+1):
+    double(v) + a rounds to the double grid d = 2^(e-52), and v is an even multiple of d, so the double sum is
+    v + a_d with a_d = a rounded to d (ties to even in units of d: a's own parity); rounding v + a_d to float then
+    adds q u when the rest r = a_d - q u is below u / 2 and (q + 1) u when it is above -- the same increment for every
+    v of the binade.  r = u / 2 exactly is a tie, broken by m's parity: one addition at a time, as are the additions
+    from 0 or a subnormal and the one that crosses into the next binade.  An addition that leaves the float where it
+    was leaves it there for good (same v, same a)."""
+    import math
+    from fractions import Fraction
+    a = 1.0 / float(np.float32(ndraws))
+    exact_a = Fraction(a)
+    v, left, moved = np.float32(0), int(count), 0
+    while left > 0:
+        bulk = 0
+        if v >= np.finfo(np.float32).tiny:
+            e = math.frexp(float(v))[1] - 1
+            u, d, top = Fraction(2) ** (e - 23), Fraction(2) ** (e - 52), Fraction(2) ** (e + 1)
+            a_d = round(exact_a / d) * d                      # Fraction.__round__: ties to even
+            q, r = divmod(a_d, u)
+            if 2 * r != u:
+                inc = q * u if 2 * r < u else (q + 1) * u
+                if inc == 0:
+                    break
+                bulk = min(left, max(0, math.ceil((top - exact_a - Fraction(float(v))) / inc)))
+                if bulk:
+                    v = np.float32(float(Fraction(float(v)) + bulk * inc))
+        if bulk == 0:
+            nv = np.float32(float(v) + a)
+            if nv == v:
+                break
+            v, bulk = nv, 1
+        left -= bulk
+        moved += bulk
+    return v, moved
+
+
+@pytest.mark.parametrize("ndraws", [2331, 2048, 1000])
+def test_replay_binades_equals_the_naive_loop(ndraws):
+    """Every count 0 .. ndraws: the binade-stepping restatement gives the float of the one-addition-at-a-time loop.
+    2331 = 7 x 3 x 111 (the addend is no power of two, every binade rounds), 2048 (every sum exact), 1000."""
+    a = 1.0 / float(np.float32(ndraws))
+    v, naive = np.float32(0), [np.float32(0)]
+    for _ in range(ndraws):
+        v = np.float32(float(v) + a)
+        naive.append(v)
+    rounded = 0
+    for c in range(ndraws + 1):
+        got, moved = replay_binades(c, ndraws)
+        assert got.dtype == np.float32 and got.view(np.uint32) == naive[c].view(np.uint32), (c, got, naive[c])
+        assert moved == c                                   # nothing stagnates this early
+        rounded += int(naive[c] != np.float32(c * a))
+    assert (rounded > 0) == (ndraws != 2048)
+
+
+def test_replay_binades_stagnation_and_ties():
+    """Draw counts beyond 2^24, count = every draw in one bin (a stand-alone C loop of v = (float)((double)v + a)
+    gave the same three floats, and 18 073 720 moving additions for the first):
+      41 943 040 = 2.5 x 2^24: in [0.5, 1) the addend is 0.4 float spacings -- the sum stops at 0.5;
+      50 331 648 = 3 x 2^24: a third of a spacing there -- 0.5 as well;
+      16 777 217: (float) rounds it to 2^24, the addend is 2^-24 and every sum up to 1.0 is exact; the last addition,
+      1 + 2^-24, is a tie and rounds to the even 1.0."""
+    v, moved = replay_binades(41943040, 41943040)
+    assert v == np.float32(0.5) and moved == 18073720
+    v, moved = replay_binades(50331648, 50331648)
+    assert v == np.float32(0.5) and moved < 50331648
+    v, moved = replay_binades(16777217, 16777217)
+    assert v == np.float32(1.0) and moved == 1 << 24
+    # short of the stagnation point the additions all count
+    v, moved = replay_binades(1 << 20, 41943040)
+    assert moved == 1 << 20 and v < np.float32(0.5)
+
+
 # ------------------------------------------------------------------------------------------ C-ABI argument checks
 
 @pytest.fixture(scope="module")
