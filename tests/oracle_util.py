@@ -571,6 +571,38 @@ def ref_pair_losses(name, fitted, reference, din, dout, loss_kind, nthreads=8, l
     return per
 
 
+def ref_loss_accepts(name):
+    """True if the reference shim's bbmref_loss knows model `name`, by its return code: a MERL-linearizer request
+    (kind 1) is refused with -2 for a known name and with -1 for an unknown one, before anything is read."""
+    lib = ref()
+    if lib is None:
+        return False
+    z = np.zeros(2, np.uint64)
+    return lib.bbmref_loss(name.encode(), None, None, 0, 1, _fp(z), _fp(z), None, 0, None, None, 1) == -2
+
+
+def np_loss(kind, din, dout, v, r):
+    """The six per-sample losses (include/loss/cosine_weighted_{l2,log}.h) in numpy, in v's dtype: float32 per
+    operation as the reference's floatRGB (log: numpy's, within an ulp of logf), or float64 (doubleRGB)."""
+    dt = v.dtype
+    c = np.maximum(din[2], dt.type(0))
+    si = np.sqrt(np.maximum(dt.type(1) - din[2] * din[2], dt.type(0)))
+    so = np.sqrt(np.maximum(dt.type(1) - dout[2] * dout[2], dt.type(0)))
+    co_ = np.maximum(dout[2], dt.type(0))
+    if kind <= 2:
+        e = ((v - r) * c).astype(np.float64)
+    else:
+        e = (np.log(dt.type(1) + v * c) - np.log(dt.type(1) + r * c)).astype(np.float64)
+    h = (e * e).sum(0)
+    if kind in (1, 4):
+        out = h * si
+    elif kind in (2, 5):
+        out = ((h * co_) * si) * so
+    else:
+        out = (h * si) * so
+    return out.astype(dt)
+
+
 def ref_batch_indices(seed, nsamples, batchsize, updates):
     """The indices the reference's bbm::batch draws (bbm::rng<Size_t>, batch.h:40-54) after construction and after
     each of `updates` update() calls -> (updates + 1, batchsize) uint64 (oracle/ref_fit.cpp: bbmref_batch_indices)."""

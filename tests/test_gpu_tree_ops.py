@@ -32,26 +32,7 @@ def _pairs(bbm, n, seed=0xF17):
     return (bbm.fill_directions(seed, 0, 0, n, mode=0), bbm.fill_directions(seed, 1, 0, n, mode=0))
 
 
-def _np_loss(kind, din, dout, v, r):
-    """The six per-sample losses (include/loss/cosine_weighted_{l2,log}.h) in numpy, in v's dtype: float32 per
-    operation as the reference's floatRGB (log: numpy's, within an ulp of logf), or float64 (doubleRGB)."""
-    dt = v.dtype
-    c = np.maximum(din[2], dt.type(0))
-    si = np.sqrt(np.maximum(dt.type(1) - din[2] * din[2], dt.type(0)))
-    so = np.sqrt(np.maximum(dt.type(1) - dout[2] * dout[2], dt.type(0)))
-    co_ = np.maximum(dout[2], dt.type(0))
-    if kind <= 2:
-        e = ((v - r) * c).astype(np.float64)
-    else:
-        e = (np.log(dt.type(1) + v * c) - np.log(dt.type(1) + r * c)).astype(np.float64)
-    h = (e * e).sum(0)
-    if kind in (1, 4):
-        out = h * si
-    elif kind in (2, 5):
-        out = ((h * co_) * si) * so
-    else:
-        out = (h * si) * so
-    return out.astype(dt)
+_np_loss = ou.np_loss     # shared with tests/test_gpu_loss_models.py
 
 
 def _composed_ct(bbm):
