@@ -42,6 +42,10 @@ SIGNATURES = {
     "bbm_hip_eval_pdf": (_I, [_I, _P, _I, _P, _P, _P, _P, _P, _P, _P, _SZ, _U32, _U32, _P, _P, _P, _P, _P]),
     "bbm_hip_sample": (_I, [_I, _P, _I, _P, _P, _P, _P, _P, _P, _SZ, _U32, _U32, _P, _P, _P, _P, _P, _P]),
     "bbm_hip_reflectance": (_I, [_I, _P, _I, _P, _P, _P, _P, _SZ, _U32, _U32, _P, _P, _P, _P]),
+    "bbm_hip_model_has_varying": (_I, [_I]),
+    "bbm_hip_eval_pdf_varying": (_I, [_I, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _SZ, _U32, _U32, _P, _P, _P, _P, _P]),
+    "bbm_hip_sample_varying": (_I, [_I, _P, _I, _P, _P, _P, _P, _P, _P, _P, _SZ, _U32, _U32, _P, _P, _P, _P, _P, _P]),
+    "bbm_hip_reflectance_varying": (_I, [_I, _P, _I, _P, _P, _P, _P, _P, _SZ, _U32, _U32, _P, _P, _P, _P]),
     "bbm_hip_model_has_f64": (_I, [_I]),
     "bbm_hip_eval_pdf_f64": (_I, [_I, _P, _I, _P, _P, _P, _P, _P, _P, _P, _SZ, _U32, _U32, _P, _P, _P, _P, _P]),
     "bbm_hip_sample_f64": (_I, [_I, _P, _I, _P, _P, _P, _P, _P, _P, _SZ, _U32, _U32, _P, _P, _P, _P, _P, _P]),

@@ -284,6 +284,51 @@ class BsdfModel:
         """True if the model has doubleRGB kernels (bbm_hip_model_has_f64)."""
         return _lib.check(_lib.load().bbm_hip_model_has_f64(self.model_id)) == 1
 
+    def has_varying(self):
+        """True if the model has per-lane parameter kernels (bbm_hip_model_has_varying): the `varying=` keyword of
+        eval / pdf / eval_pdf / sample / reflectance."""
+        return _lib.check(_lib.load().bbm_hip_model_has_varying(self.model_id)) == 1
+
+    def _varying(self, varying, n, device, f64=False):
+        """The `varying=` mapping as bbm_hip_*_varying's host array of row pointers: (ctypes array of nparams
+        pointers, the row tensors to keep alive).  Keys: an attribute name (single models) or an integer parameter
+        index (the only form for fused aggregates); values: float32 CUDA tensors of shape (n,) for one slot or (k, n)
+        with unit-stride rows for a k-slot attribute.  Raises before anything is launched."""
+        torch = _torch()
+        if f64:
+            raise TypeError("varying: per-lane parameters are floatRGB only (float32 tensors)")
+        total = self._params.size
+        rows = [None] * total
+        for key, t in dict(varying).items():
+            if isinstance(key, (int, np.integer)) and not isinstance(key, bool):
+                first, count = int(key), 1
+                if not 0 <= first < total:
+                    raise ValueError(f"{self.name}: varying index {first} out of range [0, {total})")
+            else:
+                if self.name not in ATTRIBUTES or key not in dict(ATTRIBUTES[self.name]):
+                    raise TypeError(f"{self.name}: unknown attribute '{key}'")
+                first, shape = self._slot(key)
+                count = attr_size(shape)
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or not t.is_cuda or t.device != device:
+                raise TypeError(f"{self.name}: varying[{key!r}]: expected a float32 CUDA tensor on {device}")
+            if t.dim() == 1 and count == 1:
+                got = [t]
+            elif t.dim() == 2 and t.shape[0] == count:
+                got = [t[j] for j in range(count)]
+            else:
+                want = f"({n},)" if count == 1 else f"({count}, {n})"
+                raise ValueError(f"{self.name}: varying[{key!r}]: expected shape {want}, got {tuple(t.shape)}")
+            for j, r in enumerate(got):
+                if r.numel() != n:
+                    raise ValueError(f"{self.name}: varying[{key!r}]: expected {n} lanes, got {r.numel()}")
+                if n > 1 and r.stride(0) != 1:
+                    raise ValueError(f"{self.name}: varying[{key!r}]: rows must have unit stride")
+                if rows[first + j] is not None:
+                    raise ValueError(f"{self.name}: parameter {first + j} given twice in varying")
+                rows[first + j] = r
+        arr = (ctypes.c_void_p * max(total, 1))(*[None if r is None else r.data_ptr() for r in rows])
+        return arr, [r for r in rows if r is not None]
+
     def _params_f64(self, params64):
         if params64 is None:
             return np.ascontiguousarray(self._params, dtype=np.float64)
@@ -311,8 +356,12 @@ class BsdfModel:
         return rgb, pdf
 
     def eval_pdf(self, in_, out, component=bsdf_flag.All, unit=unit_t.Radiance, mask=None, *,
-                 rgb=None, pdf=None, stream=None, mode=3, params64=None, exact=None):
+                 rgb=None, pdf=None, stream=None, mode=3, params64=None, exact=None, varying=None):
+        """varying: per-lane parameters, {attribute name or parameter index: float32 CUDA rows} (_varying); lane i
+        then evaluates the model with those parameters replaced by row[i] (bbm_hip_eval_pdf_varying)."""
         torch = _torch()
+        if varying is not None and _is_f64(in_):
+            raise TypeError("varying: per-lane parameters are floatRGB only (float32 tensors)")
         if _is_f64(in_):
             rgb, pdf = self._eval_pdf_f64(in_, out, component, unit, mask, rgb if mode & 1 else None,
                                           pdf if mode & 2 else None, stream, params64)
@@ -331,6 +380,14 @@ class BsdfModel:
         s = _stream_ptr(stream)
         _on_stream(stream, _keep, rgb, pdf)
         mid = self._call_id(exact)
+        if varying is not None:
+            vptr, vrows = self._varying(varying, n, (in_[0] if isinstance(in_, (tuple, list)) else in_).device)
+            _on_stream(stream, *vrows)
+            _lib.check(lib.bbm_hip_eval_pdf_varying(
+                mid, self._pptr(), self._params.size, vptr, ix, iy, iz, ox, oy, oz, mptr, n, int(component), int(unit),
+                rgb[0].data_ptr() if mode & 1 else None, rgb[1].data_ptr() if mode & 1 else None,
+                rgb[2].data_ptr() if mode & 1 else None, pdf.data_ptr() if mode & 2 else None, s))
+            return rgb, pdf
         if mode == 3:
             rc = lib.bbm_hip_eval_pdf(mid, self._pptr(), self._params.size, ix, iy, iz, ox, oy, oz, mptr, n,
                                       int(component), int(unit), rgb[0].data_ptr(), rgb[1].data_ptr(),
@@ -353,9 +410,9 @@ class BsdfModel:
         return self.eval_pdf(in_, out, component, unit, mask, mode=2, **kw)[1]
 
     def sample(self, out, xi, component=bsdf_flag.All, unit=unit_t.Radiance, mask=None, *, stream=None,
-               params64=None, exact=None):
+               params64=None, exact=None, varying=None):
         """BsdfSample sample(out, xi, component, unit, mask) for N (out, xi) -> BsdfSample (float64 out / xi: the
-        doubleRGB kernels, float64 direction and pdf).  exact: as eval_pdf."""
+        doubleRGB kernels, float64 direction and pdf).  exact, varying: as eval_pdf."""
         torch = _torch()
         f64 = _is_f64(out)
         dt = torch.float64 if f64 else torch.float32
@@ -376,6 +433,14 @@ class BsdfModel:
         f = torch.empty((n,), dtype=torch.int32, device=dev)
         _on_stream(stream, _keep, d, p, f)
         lib = _lib.load()
+        if varying is not None:
+            vptr, vrows = self._varying(varying, n, dev, f64=f64)
+            _on_stream(stream, *vrows)
+            _lib.check(lib.bbm_hip_sample_varying(
+                self._call_id(exact), self._pptr(), self._params.size, vptr, ox, oy, oz, x0.data_ptr(), x1.data_ptr(),
+                mptr, n, int(component), int(unit), d[0].data_ptr(), d[1].data_ptr(), d[2].data_ptr(), p.data_ptr(),
+                f.data_ptr(), _stream_ptr(stream)))
+            return BsdfSample(d, p, f)
         if f64:
             prm = self._params_f64(params64)
             fn, pp, npar = lib.bbm_hip_sample_f64, prm.ctypes.data_as(ctypes.c_void_p), prm.size
@@ -387,10 +452,12 @@ class BsdfModel:
         return BsdfSample(d, p, f)
 
     def reflectance(self, out, component=bsdf_flag.All, unit=unit_t.Radiance, mask=None, *, stream=None,
-                    params64=None, exact=None):
+                    params64=None, exact=None, varying=None):
         """Spectrum reflectance(out, component, unit, mask) for N directions -> (3, N) RGB (float64 directions:
-        the doubleRGB kernels, float64 RGB)."""
+        the doubleRGB kernels, float64 RGB).  varying: as eval_pdf."""
         torch = _torch()
+        if varying is not None and _is_f64(out):
+            raise TypeError("varying: per-lane parameters are floatRGB only (float32 tensors)")
         if _is_f64(out):
             ox, oy, oz, n = _soa(out, what="out", dtype=torch.float64)
             mptr, _keep = _mask_ptr(mask, n)
@@ -408,6 +475,13 @@ class BsdfModel:
         rgb = torch.empty((3, n), dtype=torch.float32, device=dev)
         _on_stream(stream, _keep, rgb)
         lib = _lib.load()
+        if varying is not None:
+            vptr, vrows = self._varying(varying, n, dev)
+            _on_stream(stream, *vrows)
+            _lib.check(lib.bbm_hip_reflectance_varying(
+                self._call_id(exact), self._pptr(), self._params.size, vptr, ox, oy, oz, mptr, n, int(component),
+                int(unit), rgb[0].data_ptr(), rgb[1].data_ptr(), rgb[2].data_ptr(), _stream_ptr(stream)))
+            return rgb
         _lib.check(lib.bbm_hip_reflectance(self._call_id(exact), self._pptr(), self._params.size, ox, oy, oz, mptr, n,
                                            int(component), int(unit), rgb[0].data_ptr(), rgb[1].data_ptr(),
                                            rgb[2].data_ptr(), _stream_ptr(stream)))
@@ -642,8 +716,17 @@ class AggregateModel:
             return root, 1, keep
         return build(self._children), len(self._children), keep
 
+    @staticmethod
+    def _no_varying(varying):
+        if varying is not None:
+            raise NotImplementedError("varying: per-lane parameters are not available for composed aggregates")
+
+    def has_varying(self):
+        return False
+
     def eval_pdf(self, in_, out, component=bsdf_flag.All, unit=unit_t.Radiance, mask=None, *,
-                 rgb=None, pdf=None, stream=None, mode=3):
+                 rgb=None, pdf=None, stream=None, mode=3, varying=None):
+        self._no_varying(varying)
         torch = _torch()
         f64 = _is_f64(in_)
         dt = torch.float64 if f64 else torch.float32
@@ -667,7 +750,8 @@ class AggregateModel:
     eval = BsdfModel.eval
     pdf = BsdfModel.pdf
 
-    def sample(self, out, xi, component=bsdf_flag.All, unit=unit_t.Radiance, mask=None, *, stream=None):
+    def sample(self, out, xi, component=bsdf_flag.All, unit=unit_t.Radiance, mask=None, *, stream=None, varying=None):
+        self._no_varying(varying)
         torch = _torch()
         f64 = _is_f64(out)
         dt = torch.float64 if f64 else torch.float32
@@ -689,7 +773,9 @@ class AggregateModel:
                       _stream_ptr(stream)))
         return BsdfSample(d, p, f)
 
-    def reflectance(self, out, component=bsdf_flag.All, unit=unit_t.Radiance, mask=None, *, stream=None):
+    def reflectance(self, out, component=bsdf_flag.All, unit=unit_t.Radiance, mask=None, *, stream=None,
+                    varying=None):
+        self._no_varying(varying)
         torch = _torch()
         f64 = _is_f64(out)
         dt = torch.float64 if f64 else torch.float32

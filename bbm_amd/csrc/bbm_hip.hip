@@ -333,6 +333,95 @@ int bbm_hip_reflectance(int model_id, const float* params, int nparams,
   return e->run.reflectance(a, static_cast<hipStream_t>(stream));
 }
 
+// ------------------------------------------------------------------------------- per-lane parameters (varying.hpp)
+
+// What the three per-lane calls check first, in checked_entry's order: the id, that the row has per-lane kernels, the
+// parameter count and pointer; then the uniform block (prepare) and the rows.
+static int prepare_var(int model_id, const float* params, int nparams, const float* const* varying, size_t n,
+                       EvalArgs& a, VarRows& v, const ModelEntry*& e)
+{
+  e = entry(model_id);
+  if (e && !e->run.eval_pdf_var)
+    return fail(BBM_HIP_ERR_UNSUPPORTED, std::string(e->name) + ": no per-lane parameter kernels");
+  if (const int rc = prepare(model_id, params, nparams, n, a, e)) return rc;
+  std::memset(&v, 0, sizeof(v));
+  for (int k = 0; varying && k < nparams; ++k) v.vp[k] = varying[k];
+  return BBM_HIP_OK;
+}
+
+int bbm_hip_eval_pdf_varying(int model_id, const float* params, int nparams, const float* const* varying,
+                             const float* in_x, const float* in_y, const float* in_z,
+                             const float* out_x, const float* out_y, const float* out_z,
+                             const uint8_t* mask, size_t n, uint32_t component, uint32_t unit,
+                             float* r, float* g, float* b, float* pdf, void* stream)
+{
+  (void)unit;
+  const CallExactScope mode_scope(model_id);
+  EvalVarArgs a;
+  const ModelEntry* e;
+  int rc = prepare_var(model_id, params, nparams, varying, n, a.e, a.v, e);
+  if (rc) return rc;
+  if (n == 0) return BBM_HIP_OK;
+  if ((rc = check_dirs(in_x, in_y, in_z, "in")) || (rc = check_dirs(out_x, out_y, out_z, "out"))) return rc;
+  const bool want_eval = r || g || b;
+  if (want_eval && (!r || !g || !b)) return fail(BBM_HIP_ERR_INVALID_ARG, "eval output pointer is NULL");
+  if (!want_eval && !pdf) return fail(BBM_HIP_ERR_INVALID_ARG, "every output pointer is NULL");
+  const int mode = (want_eval ? kModeEval : 0) | (pdf ? kModePdf : 0);
+  a.e.ix = in_x; a.e.iy = in_y; a.e.iz = in_z; a.e.ox = out_x; a.e.oy = out_y; a.e.oz = out_z;
+  a.e.mask = mask; a.e.r = r; a.e.g = g; a.e.b = b; a.e.pdf = pdf;
+  a.e.component = component & kFlagAll;
+  return e->run.eval_pdf_var(a, mode, static_cast<hipStream_t>(stream));
+}
+
+int bbm_hip_sample_varying(int model_id, const float* params, int nparams, const float* const* varying,
+                           const float* out_x, const float* out_y, const float* out_z,
+                           const float* xi0, const float* xi1,
+                           const uint8_t* mask, size_t n, uint32_t component, uint32_t unit,
+                           float* dir_x, float* dir_y, float* dir_z, float* pdf, uint32_t* flag, void* stream)
+{
+  (void)unit;
+  const CallExactScope mode_scope(model_id);
+  EvalArgs tmp;
+  SampleVarArgs a;
+  const ModelEntry* e;
+  int rc = prepare_var(model_id, params, nparams, varying, n, tmp, a.v, e);
+  if (rc) return rc;
+  if (n == 0) return BBM_HIP_OK;
+  if ((rc = check_dirs(out_x, out_y, out_z, "out"))) return rc;
+  if (!xi0 || !xi1) return fail(BBM_HIP_ERR_INVALID_ARG, "xi pointer is NULL");
+  if (!dir_x || !dir_y || !dir_z || !pdf || !flag) return fail(BBM_HIP_ERR_INVALID_ARG, "sample output pointer is NULL");
+  std::memset(&a.e, 0, sizeof(a.e));
+  a.e.p = tmp.p;
+  a.e.n = n;
+  a.e.ox = out_x; a.e.oy = out_y; a.e.oz = out_z; a.e.xi0 = xi0; a.e.xi1 = xi1; a.e.mask = mask;
+  a.e.dx = dir_x; a.e.dy = dir_y; a.e.dz = dir_z; a.e.pdf = pdf; a.e.flag = flag;
+  a.e.component = component & kFlagAll;
+  return e->run.sample_var(a, static_cast<hipStream_t>(stream));
+}
+
+int bbm_hip_reflectance_varying(int model_id, const float* params, int nparams, const float* const* varying,
+                                const float* out_x, const float* out_y, const float* out_z,
+                                const uint8_t* mask, size_t n, uint32_t component, uint32_t unit,
+                                float* r, float* g, float* b, void* stream)
+{
+  (void)unit;
+  const CallExactScope mode_scope(model_id);
+  EvalArgs tmp;
+  ReflVarArgs a;
+  const ModelEntry* e;
+  int rc = prepare_var(model_id, params, nparams, varying, n, tmp, a.v, e);
+  if (rc) return rc;
+  if (n == 0) return BBM_HIP_OK;
+  if ((rc = check_dirs(out_x, out_y, out_z, "out"))) return rc;
+  if (!r || !g || !b) return fail(BBM_HIP_ERR_INVALID_ARG, "reflectance output pointer is NULL");
+  std::memset(&a.e, 0, sizeof(a.e));
+  a.e.p = tmp.p;
+  a.e.n = n;
+  a.e.ox = out_x; a.e.oy = out_y; a.e.oz = out_z; a.e.mask = mask; a.e.r = r; a.e.g = g; a.e.b = b;
+  a.e.component = component & kFlagAll;
+  return e->run.reflectance_var(a, static_cast<hipStream_t>(stream));
+}
+
 // ------------------------------------------------------------------------------- doubleRGB (f64.hip)
 
 static int prepare_f64(int model_id, const double* params, int nparams, const f64::F64Launchers*& l,

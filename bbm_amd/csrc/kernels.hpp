@@ -1295,6 +1295,7 @@ int launch_loss(const LossArgs& a0, hipStream_t s)
 
 #include "check.hpp"
 #include "image.hpp"
+#include "varying.hpp"
 
 namespace bbmhip {
 
@@ -1304,6 +1305,9 @@ using CheckLauncher = int (*)(int, const CheckArgs&, double*, hipStream_t);
 using EvalLauncher = int (*)(const EvalArgs&, int, hipStream_t);
 using SampleLauncher = int (*)(const SampleArgs&, hipStream_t);
 using ReflLauncher = int (*)(const ReflArgs&, hipStream_t);
+using EvalVarLauncher = int (*)(const EvalVarArgs&, int, hipStream_t);
+using SampleVarLauncher = int (*)(const SampleVarArgs&, hipStream_t);
+using ReflVarLauncher = int (*)(const ReflVarArgs&, hipStream_t);
 
 // A composition's launchers: what a registry row (registry.hip) holds of its kernels.
 struct Launchers
@@ -1314,10 +1318,19 @@ struct Launchers
   LossLauncher loss;
   CheckLauncher check;
   ImageLauncher image;
+  // per-lane parameters (varying.hpp); all null where the composition has none (supports_varying)
+  EvalVarLauncher eval_pdf_var;
+  SampleVarLauncher sample_var;
+  ReflVarLauncher reflectance_var;
 };
 template<class M> constexpr Launchers launchers()
 {
-  return {&launch_eval_pdf<M>, &launch_sample<M>, &launch_reflectance<M>, &launch_loss<M>, &launch_check<M>, &launch_image<M>};
+  if constexpr (supports_varying<M>::value)
+    return {&launch_eval_pdf<M>, &launch_sample<M>, &launch_reflectance<M>, &launch_loss<M>, &launch_check<M>, &launch_image<M>,
+            &launch_eval_pdf_var<M>, &launch_sample_var<M>, &launch_reflectance_var<M>};
+  else
+    return {&launch_eval_pdf<M>, &launch_sample<M>, &launch_reflectance<M>, &launch_loss<M>, &launch_check<M>, &launch_image<M>,
+            nullptr, nullptr, nullptr};
 }
 
 }  // namespace bbmhip

@@ -32,6 +32,12 @@ struct check_waves<He<FRES, ERRATA, WESTIN, TAYLOR, ADAPTIVE, APPROX, SCALED>> {
 template<> struct check_waves<EpdM> { static constexpr int value = 1; };
 template<class FRES, bool ERRATA, bool WESTIN, int TAYLOR, bool ADAPTIVE, int APPROX, bool SCALED>
 struct loss_pair_waves<He<FRES, ERRATA, WESTIN, TAYLOR, ADAPTIVE, APPROX, SCALED>> { static constexpr int value = 1; };
+// Per-lane parameters (varying.hpp): not the He family, whose sample / pdf read a CDF built per launch from the
+// parameters, nor Merl, which has a table address and no parameters; an aggregate follows its second child.
+template<class FRES, bool ERRATA, bool WESTIN, int TAYLOR, bool ADAPTIVE, int APPROX, bool SCALED>
+struct supports_varying<He<FRES, ERRATA, WESTIN, TAYLOR, ADAPTIVE, APPROX, SCALED>> { static constexpr bool value = false; };
+template<> struct supports_varying<Merl> { static constexpr bool value = false; };
+template<class B> struct supports_varying<Aggregate<Lambertian, B>> { static constexpr bool value = supports_varying<B>::value; };
 // Bagher's fitting loss (config 5) runs at 8 waves per SIMD: 64 VGPRs with ~55 of the per-sample decode state spilled
 // to scratch (read back once per probe pair from L1), against 128 VGPRs and no spills at 4.  The kernel is
 // latency-bound (issue 0.40), so the doubled occupancy outweighs the spill traffic.  Measured on config 5, ms per
@@ -173,11 +179,17 @@ struct host_params<Aggregate<A, B>>
   template int launch_reflectance<M>(const ReflArgs&, hipStream_t);            \
   template int launch_loss<M>(const LossArgs&, hipStream_t);                  \
   template int launch_check<M>(int, const CheckArgs&, double*, hipStream_t);    \
-  template int launch_image<M>(const ImageArgs&, hipStream_t);
+  template int launch_image<M>(const ImageArgs&, hipStream_t);                \
+  template int launch_eval_pdf_var<M>(const EvalVarArgs&, int, hipStream_t);  \
+  template int launch_sample_var<M>(const SampleVarArgs&, hipStream_t);       \
+  template int launch_reflectance_var<M>(const ReflVarArgs&, hipStream_t);
 #define BBM_HIP_EXTERN(M)                                                       \
   extern template int launch_eval_pdf<M>(const EvalArgs&, int, hipStream_t);    \
   extern template int launch_sample<M>(const SampleArgs&, hipStream_t);         \
   extern template int launch_reflectance<M>(const ReflArgs&, hipStream_t);     \
   extern template int launch_loss<M>(const LossArgs&, hipStream_t);           \
   extern template int launch_check<M>(int, const CheckArgs&, double*, hipStream_t); \
-  extern template int launch_image<M>(const ImageArgs&, hipStream_t);
+  extern template int launch_image<M>(const ImageArgs&, hipStream_t);         \
+  extern template int launch_eval_pdf_var<M>(const EvalVarArgs&, int, hipStream_t); \
+  extern template int launch_sample_var<M>(const SampleVarArgs&, hipStream_t); \
+  extern template int launch_reflectance_var<M>(const ReflVarArgs&, hipStream_t);

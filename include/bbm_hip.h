@@ -141,6 +141,40 @@ int bbm_hip_reflectance(int model_id, const float* params, int nparams,
                         const uint8_t* mask, size_t n, uint32_t component, uint32_t unit,
                         float* r, float* g, float* b, void* stream);
 
+/* ---------------------------------------------------------------- per-lane model parameters */
+
+/* eval / pdf / sample / reflectance with a parameter vector per lane (the wide-Value backbones' packet attributes;
+ * a renderer's textured parameters).  `varying` is a HOST array of nparams DEVICE pointers: a non-NULL varying[k] is
+ * a row of n floats (any 4-byte alignment; rows that are not 16-byte aligned take the scalar kernels, as unaligned
+ * directions do), a NULL entry keeps params[k] for every lane; varying == NULL, or all entries NULL, equals the
+ * uniform call.  Lane i evaluates the model at q_i[k] = varying[k] ? varying[k][i] : params[k] and returns what the
+ * uniform entry point returns for that pair at q_i -- component, unit, mask, the exact / default mode
+ * (BBM_HIP_CALL_EXACT / _DEFAULT or the process switch) and BBM_HIP_RUNTIME_AGGREGATE on a fused aggregate's id
+ * included -- bit for bit.  The contract is on the raw parameter vector: no dependent attribute is updated and no
+ * bound is checked per lane.  The one exception to "bit for bit" is EPD where p varies: the normalization's
+ * tgammaf(1 / p) is glibc's, computed on the host for params' p; a lane whose p has other bits takes the correctly
+ * rounded tgamma of the double (as the fitting loss's probes do), which may move eval and pdf by an ulp.
+ * bbm_hip_eval_pdf_varying: r == g == b == NULL selects pdf only, pdf == NULL eval only, neither the fused form.
+ * Available for the rows bbm_hip_model_has_varying reports, 43 of the 49: not He, HeWestin, HeHolzschuch, NganHe and
+ * Aggregate<Lambertian,NganHe> (their sample / pdf read a 90-bin CDF built per launch from the parameters, which
+ * does not exist per lane) and not Merl (no parameters, only a table address): BBM_HIP_ERR_UNSUPPORTED, returned
+ * like every argument error before anything is launched.  n == 0 is a no-op.  floatRGB only. */
+int bbm_hip_model_has_varying(int model_id);            /* 1 / 0, <0 for an unknown id */
+int bbm_hip_eval_pdf_varying(int model_id, const float* params, int nparams, const float* const* varying,
+                             const float* in_x, const float* in_y, const float* in_z,
+                             const float* out_x, const float* out_y, const float* out_z,
+                             const uint8_t* mask, size_t n, uint32_t component, uint32_t unit,
+                             float* r, float* g, float* b, float* pdf, void* stream);
+int bbm_hip_sample_varying(int model_id, const float* params, int nparams, const float* const* varying,
+                           const float* out_x, const float* out_y, const float* out_z,
+                           const float* xi0, const float* xi1,
+                           const uint8_t* mask, size_t n, uint32_t component, uint32_t unit,
+                           float* dir_x, float* dir_y, float* dir_z, float* pdf, uint32_t* flag, void* stream);
+int bbm_hip_reflectance_varying(int model_id, const float* params, int nparams, const float* const* varying,
+                                const float* out_x, const float* out_y, const float* out_z,
+                                const uint8_t* mask, size_t n, uint32_t component, uint32_t unit,
+                                float* r, float* g, float* b, void* stream);
+
 /* ---------------------------------------------------------------- doubleRGB (Value = double) */
 
 /* The reference's doubleRGB configuration (backbone/native/include/backbone.h:41-42: Value = double, Spectrum =
