@@ -46,6 +46,14 @@ SIGNATURES = {
     "bbm_hip_eval_pdf_varying": (_I, [_I, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _SZ, _U32, _U32, _P, _P, _P, _P, _P]),
     "bbm_hip_sample_varying": (_I, [_I, _P, _I, _P, _P, _P, _P, _P, _P, _P, _SZ, _U32, _U32, _P, _P, _P, _P, _P, _P]),
     "bbm_hip_reflectance_varying": (_I, [_I, _P, _I, _P, _P, _P, _P, _P, _SZ, _U32, _U32, _P, _P, _P, _P]),
+    "bbm_hip_model_has_table": (_I, [_I]),
+    "bbm_hip_table_create": (_I, [_I, _P, _I, _U32, _P, _P]),
+    "bbm_hip_table_destroy": (_I, [_P]),
+    "bbm_hip_table_model": (_I, [_P]),
+    "bbm_hip_table_size": (_U32, [_P]),
+    "bbm_hip_eval_pdf_table": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _SZ, _U32, _U32, _P, _P, _P, _P, _P]),
+    "bbm_hip_sample_table": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _P, _SZ, _U32, _U32, _P, _P, _P, _P, _P, _P]),
+    "bbm_hip_reflectance_table": (_I, [_P, _I, _P, _P, _P, _P, _P, _SZ, _U32, _U32, _P, _P, _P, _P]),
     "bbm_hip_model_has_f64": (_I, [_I]),
     "bbm_hip_eval_pdf_f64": (_I, [_I, _P, _I, _P, _P, _P, _P, _P, _P, _P, _SZ, _U32, _U32, _P, _P, _P, _P, _P]),
     "bbm_hip_sample_f64": (_I, [_I, _P, _I, _P, _P, _P, _P, _P, _P, _SZ, _U32, _U32, _P, _P, _P, _P, _P, _P]),

@@ -289,6 +289,10 @@ class BsdfModel:
         eval / pdf / eval_pdf / sample / reflectance."""
         return _lib.check(_lib.load().bbm_hip_model_has_varying(self.model_id)) == 1
 
+    def has_table(self):
+        """True if the model can be held in a MaterialTable (bbm_hip_model_has_table)."""
+        return _lib.check(_lib.load().bbm_hip_model_has_table(self.model_id)) == 1
+
     def _varying(self, varying, n, device, f64=False):
         """The `varying=` mapping as bbm_hip_*_varying's host array of row pointers: (ctypes array of nparams
         pointers, the row tensors to keep alive).  Keys: an attribute name (single models) or an integer parameter
@@ -724,6 +728,9 @@ class AggregateModel:
     def has_varying(self):
         return False
 
+    def has_table(self):
+        return False
+
     def eval_pdf(self, in_, out, component=bsdf_flag.All, unit=unit_t.Radiance, mask=None, *,
                  rgb=None, pdf=None, stream=None, mode=3, varying=None):
         self._no_varying(varying)
@@ -824,6 +831,176 @@ def Aggregate(*children, fused=True, runtime=False):
             m.model_id |= _lib.RUNTIME_AGGREGATE
         return m
     return AggregateModel(*children, runtime=runtime)
+
+
+class MaterialTable:
+    """M parameter sets of one model, evaluated in one launch with a material index per lane (bbm_hip_table_*,
+    DESIGN.md §4.15): a wavefront renderer's material id per hit, the materials of one fits file over one direction
+    set.  `params` is an (M, nparams) float32 array of raw parameter vectors (BsdfModel.parameter_values()); the
+    library prepares and uploads them once, on `stream` (default: the current stream).  eval_pdf / eval / pdf /
+    sample / reflectance take the arguments of the BsdfModel methods with `material=`, an int32 CUDA tensor of one
+    index per lane, and return the same shapes; lane i gets exactly what the BsdfModel call returns for material
+    material[i].  A negative or otherwise out-of-range index is a masked lane.  floatRGB only."""
+
+    def __init__(self, model_name, params, *, runtime=False, stream=None):
+        lib = _lib.load()
+        self._handle = None
+        if not isinstance(model_name, str):
+            raise TypeError("MaterialTable: model_name must be a registry name (MaterialTable.from_models takes models)")
+        mid = lib.bbm_hip_model_id(model_name.encode())
+        if mid < 0:
+            raise ValueError(f"unknown BSDF model: {model_name}")
+        if runtime:
+            mid |= _lib.RUNTIME_AGGREGATE
+        p = np.asarray(params)
+        if p.dtype == np.float64:
+            raise TypeError("MaterialTable: material tables are floatRGB only (float32 parameters)")
+        if p.dtype != np.float32:
+            raise TypeError(f"MaterialTable: expected float32 parameters, got {p.dtype}")
+        k = _lib.check(lib.bbm_hip_model_nparams(mid))
+        if p.ndim != 2 or p.shape[0] < 1 or p.shape[1] != k:
+            raise ValueError(f"MaterialTable: {model_name}: expected an (M, {k}) array with M >= 1, got {p.shape}")
+        p = np.ascontiguousarray(p)
+        handle = ctypes.c_void_p()
+        # a row without table kernels is refused by the library before it looks at the stream: no GPU needed for that
+        sptr = _stream_ptr(stream) if lib.bbm_hip_model_has_table(mid) == 1 else None
+        _lib.check(lib.bbm_hip_table_create(mid, p.ctypes.data_as(ctypes.c_void_p), k, p.shape[0], sptr,
+                                            ctypes.byref(handle)))
+        self._handle = handle
+        self.name = model_name
+        self.model_id = mid
+        self._size = int(p.shape[0])
+
+    @classmethod
+    def from_models(cls, models, *, stream=None):
+        """A table of BsdfModels or model strings (fromString); all must be the same registry model."""
+        ms = [fromString(m) if isinstance(m, str) else m for m in models]
+        if not ms:
+            raise ValueError("MaterialTable.from_models: no models")
+        for m in ms:
+            if isinstance(m, AggregateModel):
+                raise NotImplementedError("MaterialTable: composed aggregates have no material tables (fused "
+                                          "Aggregate(Lambertian, X) models do)")
+            if not isinstance(m, BsdfModel):
+                raise TypeError("MaterialTable.from_models: expected BsdfModels or model strings")
+        if any(m.model_id != ms[0].model_id for m in ms):
+            raise ValueError("MaterialTable.from_models: every model must be the same registry model, got " +
+                             ", ".join(sorted({m.name + (" (runtime)" if m.runtime else "") for m in ms})))
+        return cls(ms[0].name, np.stack([m.parameter_values() for m in ms]).astype(np.float32), runtime=ms[0].runtime,
+                   stream=stream)
+
+    def __len__(self):
+        return self._size
+
+    def close(self):
+        """Release the table's device memory (waits for the device: launches already enqueued finish first)."""
+        h, self._handle = self._handle, None
+        if h is not None:
+            _lib.load().bbm_hip_table_destroy(h)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:       # interpreter shutdown
+            pass
+
+    def _live(self):
+        if self._handle is None:
+            raise ValueError("MaterialTable: the table is closed")
+        return self._handle
+
+    @staticmethod
+    def _flags(exact):
+        return 0 if exact is None else (_lib.CALL_EXACT if exact else _lib.CALL_DEFAULT)
+
+    @staticmethod
+    def _material(material, n, device):
+        """The index tensor's pointer: int32, on the inputs' device, n elements with unit stride.  Its bits are read
+        as uint32, so a negative index is out of range: a masked lane."""
+        torch = _torch()
+        if not isinstance(material, torch.Tensor) or material.dtype != torch.int32 or not material.is_cuda or \
+                material.device != device:
+            raise TypeError(f"material: expected an int32 CUDA tensor on {device}")
+        if material.dim() != 1 or material.numel() != n:
+            raise ValueError(f"material: expected {n} indices, got shape {tuple(material.shape)}")
+        if n > 1 and material.stride(0) != 1:
+            raise ValueError("material: indices must have unit stride")
+        return material.data_ptr()
+
+    def eval_pdf(self, in_, out, component=bsdf_flag.All, unit=unit_t.Radiance, mask=None, *, material,
+                 rgb=None, pdf=None, stream=None, mode=3, exact=None):
+        torch = _torch()
+        if _is_f64(in_) or _is_f64(out):
+            raise TypeError("MaterialTable: material tables are floatRGB only (float32 tensors)")
+        h = self._live()
+        ix, iy, iz, n = _soa(in_, what="in")
+        ox, oy, oz, _ = _soa(out, n, what="out")
+        dev = (in_[0] if isinstance(in_, (tuple, list)) else in_).device
+        idx = self._material(material, n, dev)
+        mptr, _keep = _mask_ptr(mask, n)
+        if mode & 1:
+            rgb = torch.empty((3, n), dtype=torch.float32, device=dev) if rgb is None else \
+                _out_rows(rgb, 3, n, dev, "rgb")
+        if mode & 2:
+            pdf = torch.empty((n,), dtype=torch.float32, device=dev) if pdf is None else \
+                _out_rows(pdf, 0, n, dev, "pdf")
+        _on_stream(stream, _keep, rgb, pdf, material)
+        _lib.check(_lib.load().bbm_hip_eval_pdf_table(
+            h, self._flags(exact), idx, ix, iy, iz, ox, oy, oz, mptr, n, int(component), int(unit),
+            rgb[0].data_ptr() if mode & 1 else None, rgb[1].data_ptr() if mode & 1 else None,
+            rgb[2].data_ptr() if mode & 1 else None, pdf.data_ptr() if mode & 2 else None, _stream_ptr(stream)))
+        return rgb, pdf
+
+    def eval(self, in_, out, component=bsdf_flag.All, unit=unit_t.Radiance, mask=None, **kw):
+        return self.eval_pdf(in_, out, component, unit, mask, mode=1, **kw)[0]
+
+    def pdf(self, in_, out, component=bsdf_flag.All, unit=unit_t.Radiance, mask=None, **kw):
+        return self.eval_pdf(in_, out, component, unit, mask, mode=2, **kw)[1]
+
+    def sample(self, out, xi, component=bsdf_flag.All, unit=unit_t.Radiance, mask=None, *, material, stream=None,
+               exact=None):
+        torch = _torch()
+        if _is_f64(out):
+            raise TypeError("MaterialTable: material tables are floatRGB only (float32 tensors)")
+        h = self._live()
+        ox, oy, oz, n = _soa(out, what="out")
+        if isinstance(xi, (tuple, list)):
+            x0, x1 = xi
+        else:
+            if xi.dim() != 2 or xi.shape[0] != 2:
+                raise ValueError("xi: expected a (2, N) tensor")
+            x0, x1 = xi[0], xi[1]
+        for x in (x0, x1):
+            if x.dtype != torch.float32 or not x.is_cuda or x.numel() != n or x.stride(0) != 1:
+                raise TypeError("xi: expected float32 CUDA rows with one entry per direction")
+        dev = x0.device
+        idx = self._material(material, n, dev)
+        mptr, _keep = _mask_ptr(mask, n)
+        d = torch.empty((3, n), dtype=torch.float32, device=dev)
+        p = torch.empty((n,), dtype=torch.float32, device=dev)
+        f = torch.empty((n,), dtype=torch.int32, device=dev)
+        _on_stream(stream, _keep, d, p, f, material)
+        _lib.check(_lib.load().bbm_hip_sample_table(
+            h, self._flags(exact), idx, ox, oy, oz, x0.data_ptr(), x1.data_ptr(), mptr, n, int(component), int(unit),
+            d[0].data_ptr(), d[1].data_ptr(), d[2].data_ptr(), p.data_ptr(), f.data_ptr(), _stream_ptr(stream)))
+        return BsdfSample(d, p, f)
+
+    def reflectance(self, out, component=bsdf_flag.All, unit=unit_t.Radiance, mask=None, *, material, stream=None,
+                    exact=None):
+        torch = _torch()
+        if _is_f64(out):
+            raise TypeError("MaterialTable: material tables are floatRGB only (float32 tensors)")
+        h = self._live()
+        ox, oy, oz, n = _soa(out, what="out")
+        dev = (out[0] if isinstance(out, (tuple, list)) else out).device
+        idx = self._material(material, n, dev)
+        mptr, _keep = _mask_ptr(mask, n)
+        rgb = torch.empty((3, n), dtype=torch.float32, device=dev)
+        _on_stream(stream, _keep, rgb, material)
+        _lib.check(_lib.load().bbm_hip_reflectance_table(
+            h, self._flags(exact), idx, ox, oy, oz, mptr, n, int(component), int(unit), rgb[0].data_ptr(),
+            rgb[1].data_ptr(), rgb[2].data_ptr(), _stream_ptr(stream)))
+        return rgb
 
 
 def _make_ctor(name):

@@ -5,7 +5,9 @@
 
 #include <cmath>
 #include <cstring>
+#include <memory>
 #include <string>
+#include <vector>
 
 #include "../../include/bbm_hip.h"
 #include "registry.hpp"
@@ -420,6 +422,203 @@ int bbm_hip_reflectance_varying(int model_id, const float* params, int nparams, 
   a.e.ox = out_x; a.e.oy = out_y; a.e.oz = out_z; a.e.mask = mask; a.e.r = r; a.e.g = g; a.e.b = b;
   a.e.component = component & kFlagAll;
   return e->run.reflectance_var(a, static_cast<hipStream_t>(stream));
+}
+
+// ------------------------------------------------------------------------------- material tables (table.hpp)
+
+}  // extern "C"
+
+// One model's parameter sets as prepared blocks in device memory (table.hpp).  `raw` is what eval alone and
+// reflectance read, `prepared` what eval + pdf, pdf and sample read (host_params applied); one allocation where the
+// two are equal, which is every row but EPD.  first_*: material 0's blocks, the kernarg fallback of a lane whose
+// index is out of range, with the aggregate mode slot of the id given to create.
+struct bbm_hip_table
+{
+  int model_id;
+  const ModelEntry* e;
+  uint32_t count;
+  float* raw;
+  float* prepared;
+  ParamBlock first_raw, first_prepared;
+};
+
+namespace {
+
+int table_call(const bbm_hip_table* t, int call_flags, size_t n, const uint32_t* material)
+{
+  if (!t) return fail(BBM_HIP_ERR_INVALID_ARG, "table is NULL");
+  if ((call_flags & ~(BBM_HIP_CALL_EXACT | BBM_HIP_CALL_DEFAULT)) != 0 ||
+      call_flags == (BBM_HIP_CALL_EXACT | BBM_HIP_CALL_DEFAULT))
+    return fail(BBM_HIP_ERR_INVALID_ARG, "call_flags must be 0, BBM_HIP_CALL_EXACT or BBM_HIP_CALL_DEFAULT");
+  if (n > 0 && !material) return fail(BBM_HIP_ERR_INVALID_ARG, "material index pointer is NULL");
+  return BBM_HIP_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int bbm_hip_table_create(int model_id, const float* params, int nparams, uint32_t nmaterials, void* stream,
+                         bbm_hip_table** out)
+{
+  const ModelEntry* e = entry(model_id);
+  if (e && !e->run.eval_pdf_tab)
+    return fail(BBM_HIP_ERR_UNSUPPORTED, std::string(e->name) + ": no material-table kernels");
+  if (const int rc = checked_entry(model_id, nparams, params, false, false, e)) return rc;
+  if (model_id & (BBM_HIP_CALL_EXACT | BBM_HIP_CALL_DEFAULT))
+    return fail(BBM_HIP_ERR_INVALID_ARG, "BBM_HIP_CALL_* belongs to the batch calls' call_flags, not to a table's model id");
+  if (!params) return fail(BBM_HIP_ERR_INVALID_ARG, "params is NULL");
+  if (nmaterials == 0) return fail(BBM_HIP_ERR_INVALID_ARG, "a table needs at least one material");
+  if (!out) return fail(BBM_HIP_ERR_INVALID_ARG, "out is NULL");
+  *out = nullptr;
+  const hipStream_t s = static_cast<hipStream_t>(stream);
+  std::unique_ptr<bbm_hip_table> t(new bbm_hip_table{model_id, e, nmaterials, nullptr, nullptr, {}, {}});
+  std::vector<float> raw, prepared;
+  size_t stride = 0;
+  bool same = true;
+  for (uint32_t m = 0; m < nmaterials; ++m)
+  {
+    ParamBlock in;
+    std::memset(&in, 0, sizeof(in));
+    for (int k = 0; k < nparams; ++k) in.v[k] = params[size_t(m) * size_t(nparams) + size_t(k)];
+    in.v[kAggregateModeSlot] = runtime_id(model_id) ? 1.0f : 0.0f;
+    TableBlocks b;
+    if (const int rc = e->run.table_prepare(in, m == 0, s, b)) return rc;
+    if (m == 0)
+    {
+      stride = size_t(table_stride(b.slots));
+      raw.assign(size_t(nmaterials) * stride, 0.0f);
+      prepared.assign(size_t(nmaterials) * stride, 0.0f);
+      t->first_raw = b.raw;
+      t->first_prepared = b.prepared;
+    }
+    std::memcpy(&raw[size_t(m) * stride], b.raw.v, size_t(b.slots) * sizeof(float));
+    std::memcpy(&prepared[size_t(m) * stride], b.prepared.v, size_t(b.slots) * sizeof(float));
+    same = same && std::memcmp(b.raw.v, b.prepared.v, size_t(b.slots) * sizeof(float)) == 0;
+  }
+  // upload in stream order; the host copies are released once the stream has taken them
+  const size_t bytes = raw.size() * sizeof(float);
+  const auto upload = [&](const std::vector<float>& h, float*& d) {
+    hipError_t err = hipMalloc(reinterpret_cast<void**>(&d), bytes);
+    if (err == hipSuccess) err = hipMemcpyAsync(d, h.data(), bytes, hipMemcpyHostToDevice, s);
+    return err;
+  };
+  hipError_t err = upload(prepared, t->prepared);
+  if (err == hipSuccess && !same) err = upload(raw, t->raw);
+  if (err == hipSuccess) err = hipStreamSynchronize(s);
+  if (err != hipSuccess)
+  {
+    (void)hipGetLastError();
+    if (t->raw) (void)hipFree(t->raw);
+    if (t->prepared) (void)hipFree(t->prepared);
+    return fail(BBM_HIP_ERR_HIP, std::string("material table upload failed: ") + hipGetErrorString(err));
+  }
+  if (same) t->raw = t->prepared;
+  *out = t.release();
+  return BBM_HIP_OK;
+}
+
+int bbm_hip_table_destroy(bbm_hip_table* t)
+{
+  if (!t) return BBM_HIP_OK;
+  // hipFree waits for the device, so launches already enqueued on the table finish first
+  hipError_t err = hipFree(t->prepared);
+  if (t->raw != t->prepared)
+  {
+    const hipError_t err2 = hipFree(t->raw);
+    if (err == hipSuccess) err = err2;
+  }
+  delete t;
+  if (err != hipSuccess) return fail(BBM_HIP_ERR_HIP, std::string("hipFree failed: ") + hipGetErrorString(err));
+  return BBM_HIP_OK;
+}
+
+int bbm_hip_table_model(const bbm_hip_table* t)
+{
+  return t ? t->model_id : fail(BBM_HIP_ERR_INVALID_ARG, "table is NULL");
+}
+
+uint32_t bbm_hip_table_size(const bbm_hip_table* t) { return t ? t->count : 0u; }
+
+int bbm_hip_eval_pdf_table(const bbm_hip_table* t, int call_flags, const uint32_t* material,
+                           const float* in_x, const float* in_y, const float* in_z,
+                           const float* out_x, const float* out_y, const float* out_z,
+                           const uint8_t* mask, size_t n, uint32_t component, uint32_t unit,
+                           float* r, float* g, float* b, float* pdf, void* stream)
+{
+  (void)unit;
+  int rc = table_call(t, call_flags, n, material);
+  if (rc) return rc;
+  if (n == 0) return BBM_HIP_OK;
+  const CallExactScope mode_scope(call_flags);
+  if ((rc = check_dirs(in_x, in_y, in_z, "in")) || (rc = check_dirs(out_x, out_y, out_z, "out"))) return rc;
+  const bool want_eval = r || g || b;
+  if (want_eval && (!r || !g || !b)) return fail(BBM_HIP_ERR_INVALID_ARG, "eval output pointer is NULL");
+  if (!want_eval && !pdf) return fail(BBM_HIP_ERR_INVALID_ARG, "every output pointer is NULL");
+  const int mode = (want_eval ? kModeEval : 0) | (pdf ? kModePdf : 0);
+  EvalTabArgs a;
+  std::memset(&a, 0, sizeof(a));
+  // host_params runs for the uniform call only where a pdf is asked for (launch_mode)
+  a.e.p = (mode & kModePdf) ? t->first_prepared : t->first_raw;
+  a.t.blocks = (mode & kModePdf) ? t->prepared : t->raw;
+  a.t.material = material;
+  a.t.count = t->count;
+  a.e.n = n;
+  a.e.ix = in_x; a.e.iy = in_y; a.e.iz = in_z; a.e.ox = out_x; a.e.oy = out_y; a.e.oz = out_z;
+  a.e.mask = mask; a.e.r = r; a.e.g = g; a.e.b = b; a.e.pdf = pdf;
+  a.e.component = component & kFlagAll;
+  return t->e->run.eval_pdf_tab(a, mode, static_cast<hipStream_t>(stream));
+}
+
+int bbm_hip_sample_table(const bbm_hip_table* t, int call_flags, const uint32_t* material,
+                         const float* out_x, const float* out_y, const float* out_z,
+                         const float* xi0, const float* xi1,
+                         const uint8_t* mask, size_t n, uint32_t component, uint32_t unit,
+                         float* dir_x, float* dir_y, float* dir_z, float* pdf, uint32_t* flag, void* stream)
+{
+  (void)unit;
+  int rc = table_call(t, call_flags, n, material);
+  if (rc) return rc;
+  if (n == 0) return BBM_HIP_OK;
+  const CallExactScope mode_scope(call_flags);
+  if ((rc = check_dirs(out_x, out_y, out_z, "out"))) return rc;
+  if (!xi0 || !xi1) return fail(BBM_HIP_ERR_INVALID_ARG, "xi pointer is NULL");
+  if (!dir_x || !dir_y || !dir_z || !pdf || !flag) return fail(BBM_HIP_ERR_INVALID_ARG, "sample output pointer is NULL");
+  SampleTabArgs a;
+  std::memset(&a, 0, sizeof(a));
+  a.e.p = t->first_prepared;
+  a.t.blocks = t->prepared;
+  a.t.material = material;
+  a.t.count = t->count;
+  a.e.n = n;
+  a.e.ox = out_x; a.e.oy = out_y; a.e.oz = out_z; a.e.xi0 = xi0; a.e.xi1 = xi1; a.e.mask = mask;
+  a.e.dx = dir_x; a.e.dy = dir_y; a.e.dz = dir_z; a.e.pdf = pdf; a.e.flag = flag;
+  a.e.component = component & kFlagAll;
+  return t->e->run.sample_tab(a, static_cast<hipStream_t>(stream));
+}
+
+int bbm_hip_reflectance_table(const bbm_hip_table* t, int call_flags, const uint32_t* material,
+                              const float* out_x, const float* out_y, const float* out_z,
+                              const uint8_t* mask, size_t n, uint32_t component, uint32_t unit,
+                              float* r, float* g, float* b, void* stream)
+{
+  (void)unit;
+  int rc = table_call(t, call_flags, n, material);
+  if (rc) return rc;
+  if (n == 0) return BBM_HIP_OK;
+  const CallExactScope mode_scope(call_flags);
+  if ((rc = check_dirs(out_x, out_y, out_z, "out"))) return rc;
+  if (!r || !g || !b) return fail(BBM_HIP_ERR_INVALID_ARG, "reflectance output pointer is NULL");
+  ReflTabArgs a;
+  std::memset(&a, 0, sizeof(a));
+  a.e.p = t->first_raw;
+  a.t.blocks = t->raw;
+  a.t.material = material;
+  a.t.count = t->count;
+  a.e.n = n;
+  a.e.ox = out_x; a.e.oy = out_y; a.e.oz = out_z; a.e.mask = mask; a.e.r = r; a.e.g = g; a.e.b = b;
+  a.e.component = component & kFlagAll;
+  return t->e->run.reflectance_tab(a, static_cast<hipStream_t>(stream));
 }
 
 // ------------------------------------------------------------------------------- doubleRGB (f64.hip)

@@ -1296,6 +1296,7 @@ int launch_loss(const LossArgs& a0, hipStream_t s)
 #include "check.hpp"
 #include "image.hpp"
 #include "varying.hpp"
+#include "table.hpp"
 
 namespace bbmhip {
 
@@ -1308,6 +1309,10 @@ using ReflLauncher = int (*)(const ReflArgs&, hipStream_t);
 using EvalVarLauncher = int (*)(const EvalVarArgs&, int, hipStream_t);
 using SampleVarLauncher = int (*)(const SampleVarArgs&, hipStream_t);
 using ReflVarLauncher = int (*)(const ReflVarArgs&, hipStream_t);
+using TablePrepare = int (*)(const ParamBlock&, bool, hipStream_t, TableBlocks&);
+using EvalTabLauncher = int (*)(const EvalTabArgs&, int, hipStream_t);
+using SampleTabLauncher = int (*)(const SampleTabArgs&, hipStream_t);
+using ReflTabLauncher = int (*)(const ReflTabArgs&, hipStream_t);
 
 // A composition's launchers: what a registry row (registry.hip) holds of its kernels.
 struct Launchers
@@ -1322,15 +1327,21 @@ struct Launchers
   EvalVarLauncher eval_pdf_var;
   SampleVarLauncher sample_var;
   ReflVarLauncher reflectance_var;
+  // material tables (table.hpp): a material's block on the host and the three kernels; null for the same rows
+  TablePrepare table_prepare;
+  EvalTabLauncher eval_pdf_tab;
+  SampleTabLauncher sample_tab;
+  ReflTabLauncher reflectance_tab;
 };
 template<class M> constexpr Launchers launchers()
 {
   if constexpr (supports_varying<M>::value)
     return {&launch_eval_pdf<M>, &launch_sample<M>, &launch_reflectance<M>, &launch_loss<M>, &launch_check<M>, &launch_image<M>,
-            &launch_eval_pdf_var<M>, &launch_sample_var<M>, &launch_reflectance_var<M>};
+            &launch_eval_pdf_var<M>, &launch_sample_var<M>, &launch_reflectance_var<M>,
+            &table_prepare<M>, &launch_eval_pdf_tab<M>, &launch_sample_tab<M>, &launch_reflectance_tab<M>};
   else
     return {&launch_eval_pdf<M>, &launch_sample<M>, &launch_reflectance<M>, &launch_loss<M>, &launch_check<M>, &launch_image<M>,
-            nullptr, nullptr, nullptr};
+            nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
 }
 
 }  // namespace bbmhip

@@ -38,6 +38,10 @@ template<class FRES, bool ERRATA, bool WESTIN, int TAYLOR, bool ADAPTIVE, int AP
 struct supports_varying<He<FRES, ERRATA, WESTIN, TAYLOR, ADAPTIVE, APPROX, SCALED>> { static constexpr bool value = false; };
 template<> struct supports_varying<Merl> { static constexpr bool value = false; };
 template<class B> struct supports_varying<Aggregate<Lambertian, B>> { static constexpr bool value = supports_varying<B>::value; };
+// Material tables (table.hpp): the slots a block keeps per material.  EPD's constructor also reads the two slots
+// host_params<EpdM> writes behind its parameters; an aggregate's block is its children's, one after the other.
+template<> struct table_slots<EpdM> { static constexpr int value = EpdM::kParams + 2; };
+template<class B> struct table_slots<Aggregate<Lambertian, B>> { static constexpr int value = Lambertian::kParams + table_slots<B>::value; };
 // Bagher's fitting loss (config 5) runs at 8 waves per SIMD: 64 VGPRs with ~55 of the per-sample decode state spilled
 // to scratch (read back once per probe pair from L1), against 128 VGPRs and no spills at 4.  The kernel is
 // latency-bound (issue 0.40), so the doubled occupancy outweighs the spill traffic.  Measured on config 5, ms per
@@ -182,7 +186,11 @@ struct host_params<Aggregate<A, B>>
   template int launch_image<M>(const ImageArgs&, hipStream_t);                \
   template int launch_eval_pdf_var<M>(const EvalVarArgs&, int, hipStream_t);  \
   template int launch_sample_var<M>(const SampleVarArgs&, hipStream_t);       \
-  template int launch_reflectance_var<M>(const ReflVarArgs&, hipStream_t);
+  template int launch_reflectance_var<M>(const ReflVarArgs&, hipStream_t);    \
+  template int table_prepare<M>(const ParamBlock&, bool, hipStream_t, TableBlocks&); \
+  template int launch_eval_pdf_tab<M>(const EvalTabArgs&, int, hipStream_t);  \
+  template int launch_sample_tab<M>(const SampleTabArgs&, hipStream_t);       \
+  template int launch_reflectance_tab<M>(const ReflTabArgs&, hipStream_t);
 #define BBM_HIP_EXTERN(M)                                                       \
   extern template int launch_eval_pdf<M>(const EvalArgs&, int, hipStream_t);    \
   extern template int launch_sample<M>(const SampleArgs&, hipStream_t);         \
@@ -192,4 +200,8 @@ struct host_params<Aggregate<A, B>>
   extern template int launch_image<M>(const ImageArgs&, hipStream_t);         \
   extern template int launch_eval_pdf_var<M>(const EvalVarArgs&, int, hipStream_t); \
   extern template int launch_sample_var<M>(const SampleVarArgs&, hipStream_t); \
-  extern template int launch_reflectance_var<M>(const ReflVarArgs&, hipStream_t);
+  extern template int launch_reflectance_var<M>(const ReflVarArgs&, hipStream_t); \
+  extern template int table_prepare<M>(const ParamBlock&, bool, hipStream_t, TableBlocks&); \
+  extern template int launch_eval_pdf_tab<M>(const EvalTabArgs&, int, hipStream_t); \
+  extern template int launch_sample_tab<M>(const SampleTabArgs&, hipStream_t); \
+  extern template int launch_reflectance_tab<M>(const ReflTabArgs&, hipStream_t);

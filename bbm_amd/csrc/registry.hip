@@ -335,6 +335,13 @@ int bbm_hip_model_has_varying(int model_id)
   return e->run.eval_pdf_var ? 1 : 0;
 }
 
+int bbm_hip_model_has_table(int model_id)
+{
+  const ModelEntry* e = entry(model_id);
+  if (!e) return unknown_id(model_id);
+  return e->run.eval_pdf_tab ? 1 : 0;
+}
+
 const char* bbm_hip_model_layout(int model_id)
 {
   const ModelEntry* e = entry(model_id);

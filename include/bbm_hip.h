@@ -175,6 +175,52 @@ int bbm_hip_reflectance_varying(int model_id, const float* params, int nparams, 
                                 const uint8_t* mask, size_t n, uint32_t component, uint32_t unit,
                                 float* r, float* g, float* b, void* stream);
 
+/* ---------------------------------------------------------------- material tables */
+
+/* eval / pdf / sample / reflectance over many parameter sets of ONE model in one launch, a 4-byte index per lane (a
+ * wavefront renderer's material id per hit, the materials of one fits file over one direction set).
+ * bbm_hip_table_create takes nmaterials x nparams HOST floats, row-major, and runs per material what the uniform
+ * entry points run on their parameter block before a launch (the model's validation and host-side derived data,
+ * EPD's tgammaf(1 / p) included; BBM_HIP_RUNTIME_AGGREGATE on a fused aggregate's id is kept for every call on the
+ * table; BBM_HIP_CALL_* bits in the id are BBM_HIP_ERR_INVALID_ARG: they belong to call_flags).  The prepared blocks
+ * are uploaded in stream order on `stream` into device memory the handle owns; create returns after the upload, so
+ * `params` may be released at once.  A table is not updated in place.  bbm_hip_table_destroy may be called as soon
+ * as the table's last launch has been enqueued (it waits for the device); NULL is a no-op.
+ * The three batch calls take the arguments of their _varying namesakes with (table, call_flags, material) in place
+ * of (model_id, params, nparams, varying): call_flags is 0, BBM_HIP_CALL_EXACT or BBM_HIP_CALL_DEFAULT, `material`
+ * n DEVICE indices (any 4-byte alignment; an index array that is not 16-byte aligned takes the scalar kernel, as
+ * unaligned directions do).  Lane i returns what the uniform entry point returns for that pair with material
+ * material[i]'s parameter vector -- component, unit, mask, the exact / default mode and the runtime-aggregate
+ * semantics included -- bit for bit on every supported row, EPD included.  A lane with material[i] >= nmaterials
+ * reads nothing from the table and returns what the uniform call returns for a lane with mask[i] == 0: an index
+ * array filled with -1 is a batch of masked lanes, never an out-of-bounds read.  The contract is on the raw parameter
+ * vectors: no dependent attribute is updated and no bound is checked.  bbm_hip_eval_pdf_table selects its mode by
+ * NULL outputs as bbm_hip_eval_pdf_varying does.  Available for the rows bbm_hip_model_has_table reports, which are
+ * those of bbm_hip_model_has_varying (the He family and NganHe would need a sampling CDF per material and
+ * component, Merl has no parameters): BBM_HIP_ERR_UNSUPPORTED from create.  Every argument error is returned before
+ * anything is allocated or launched; n == 0 is a no-op.  floatRGB only. */
+typedef struct bbm_hip_table bbm_hip_table;
+int bbm_hip_model_has_table(int model_id);              /* 1 / 0, <0 for an unknown id */
+int bbm_hip_table_create(int model_id, const float* params, int nparams, uint32_t nmaterials, void* stream,
+                         bbm_hip_table** out);
+int bbm_hip_table_destroy(bbm_hip_table* table);
+int bbm_hip_table_model(const bbm_hip_table* table);    /* the id given to create */
+uint32_t bbm_hip_table_size(const bbm_hip_table* table); /* nmaterials */
+int bbm_hip_eval_pdf_table(const bbm_hip_table* table, int call_flags, const uint32_t* material,
+                           const float* in_x, const float* in_y, const float* in_z,
+                           const float* out_x, const float* out_y, const float* out_z,
+                           const uint8_t* mask, size_t n, uint32_t component, uint32_t unit,
+                           float* r, float* g, float* b, float* pdf, void* stream);
+int bbm_hip_sample_table(const bbm_hip_table* table, int call_flags, const uint32_t* material,
+                         const float* out_x, const float* out_y, const float* out_z,
+                         const float* xi0, const float* xi1,
+                         const uint8_t* mask, size_t n, uint32_t component, uint32_t unit,
+                         float* dir_x, float* dir_y, float* dir_z, float* pdf, uint32_t* flag, void* stream);
+int bbm_hip_reflectance_table(const bbm_hip_table* table, int call_flags, const uint32_t* material,
+                              const float* out_x, const float* out_y, const float* out_z,
+                              const uint8_t* mask, size_t n, uint32_t component, uint32_t unit,
+                              float* r, float* g, float* b, void* stream);
+
 /* ---------------------------------------------------------------- doubleRGB (Value = double) */
 
 /* The reference's doubleRGB configuration (backbone/native/include/backbone.h:41-42: Value = double, Spectrum =
