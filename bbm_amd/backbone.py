@@ -129,6 +129,51 @@ def _on_stream(stream, *tensors):
             t.record_stream(stream)
 
 
+def _sample_eval_inputs(out, xi):
+    """sample_eval's inputs, checked before anything is allocated or launched: (out's x, y, z pointers, n, the two
+    xi rows).  floatRGB only: float64 tensors are a TypeError, as for `varying=`."""
+    torch = _torch()
+    if _is_f64(out) or _is_f64(xi):
+        raise TypeError("sample_eval: floatRGB only (float32 tensors)")
+    ox, oy, oz, n = _soa(out, what="out")
+    if isinstance(xi, (tuple, list)):
+        if len(xi) != 2:
+            raise ValueError("xi: expected two rows")
+        x0, x1 = xi
+    else:
+        if not isinstance(xi, torch.Tensor) or xi.dim() != 2 or xi.shape[0] != 2:
+            raise ValueError("xi: expected a (2, N) tensor")
+        x0, x1 = xi[0], xi[1]
+    for x in (x0, x1):
+        if not isinstance(x, torch.Tensor) or x.dtype != torch.float32 or not x.is_cuda or x.numel() != n or \
+                x.dim() != 1 or (n > 1 and x.stride(0) != 1):
+            raise TypeError("xi: expected float32 CUDA rows with one entry per direction")
+    return ox, oy, oz, n, x0, x1
+
+
+def _sample_eval_outputs(n, device, value, weight):
+    """(direction, pdf, flag, value or None, weight or None) for one sample_eval call."""
+    torch = _torch()
+    d = torch.empty((3, n), dtype=torch.float32, device=device)
+    p = torch.empty((n,), dtype=torch.float32, device=device)
+    f = torch.empty((n,), dtype=torch.int32, device=device)
+    v = torch.empty((3, n), dtype=torch.float32, device=device) if value else None
+    w = torch.empty((3, n), dtype=torch.float32, device=device) if weight else None
+    return d, p, f, v, w
+
+
+def _row_ptrs(t):
+    """The three row pointers of a (3, N) output, or three NULLs for a group that is not stored."""
+    return (None, None, None) if t is None else (t[0].data_ptr(), t[1].data_ptr(), t[2].data_ptr())
+
+
+def _weight(value, direction, pdf):
+    """sample_eval's weight with torch float32 ops: value * direction_z / pdf where pdf > epsilon(float32), else 0."""
+    torch = _torch()
+    eps = float(np.finfo(np.float32).eps)
+    return torch.where(pdf > eps, (value * direction[2]) / pdf, torch.zeros_like(value))
+
+
 def model_names():
     """Models available in the loaded HIP library (BBM_EXPORT_BSDFMODEL registry equivalent)."""
     lib = _lib.load()
@@ -455,6 +500,24 @@ class BsdfModel:
                       _stream_ptr(stream)))
         return BsdfSample(d, p, f)
 
+    def sample_eval(self, out, xi, component=bsdf_flag.All, unit=unit_t.Radiance, mask=None, *, value=True,
+                    weight=True, stream=None, exact=None):
+        """One BSDF call per bounce in one launch (bbm_hip_sample_eval): -> (BsdfSample, value, weight).  The sample is
+        sample(out, xi)'s, value (3, N) is eval_pdf(sample.direction, out)[0] and weight (3, N) is
+        value * direction_z / pdf where pdf > epsilon(float32), else 0 -- each bit for bit what the staged calls give,
+        without the sampled direction's round trip through memory.  value=False / weight=False: that group is not
+        stored and None is returned for it.  floatRGB only."""
+        ox, oy, oz, n, x0, x1 = _sample_eval_inputs(out, xi)
+        mptr, _keep = _mask_ptr(mask, n)
+        outs = _sample_eval_outputs(n, x0.device, value, weight)
+        _on_stream(stream, _keep, *outs)
+        d, p, f, v, w = outs
+        _lib.check(_lib.load().bbm_hip_sample_eval(
+            self._call_id(exact), self._pptr(), self._params.size, ox, oy, oz, x0.data_ptr(), x1.data_ptr(), mptr, n,
+            int(component), int(unit), d[0].data_ptr(), d[1].data_ptr(), d[2].data_ptr(), p.data_ptr(), f.data_ptr(),
+            *_row_ptrs(v), *_row_ptrs(w), _stream_ptr(stream)))
+        return BsdfSample(d, p, f), v, w
+
     def reflectance(self, out, component=bsdf_flag.All, unit=unit_t.Radiance, mask=None, *, stream=None,
                     params64=None, exact=None, varying=None):
         """Spectrum reflectance(out, component, unit, mask) for N directions -> (3, N) RGB (float64 directions:
@@ -780,6 +843,28 @@ class AggregateModel:
                       _stream_ptr(stream)))
         return BsdfSample(d, p, f)
 
+    def sample_eval(self, out, xi, component=bsdf_flag.All, unit=unit_t.Radiance, mask=None, *, value=True,
+                    weight=True, stream=None, exact=None):
+        """BsdfModel.sample_eval for a composed or runtime tree -- staged: a tree has no fused kernel, so this runs
+        the tree's own sample and eval_pdf on the GPU (two launches, the direction goes through memory) and forms
+        the weight with torch float32 ops under the same rule (value * direction_z / pdf where pdf > epsilon, else
+        0).  -> (BsdfSample, value or None, weight or None).  floatRGB only; a tree has no exact mode of its own, so
+        exact must be None."""
+        torch = _torch()
+        if exact is not None:
+            raise NotImplementedError("sample_eval: composed aggregates follow the process-wide mode (exact=None)")
+        _sample_eval_inputs(out, xi)
+        s = self.sample(out, xi, component, unit, mask, stream=stream)
+        if not (value or weight):
+            return s, None, None
+        v = self.eval_pdf(s.direction, out, component, unit, mask, stream=stream, mode=1)[0]
+        w = None
+        if weight:
+            run = torch.cuda.current_stream() if stream is None else stream
+            with torch.cuda.stream(run):
+                w = _weight(v, s.direction, s.pdf)
+        return s, (v if value else None), w
+
     def reflectance(self, out, component=bsdf_flag.All, unit=unit_t.Radiance, mask=None, *, stream=None,
                     varying=None):
         self._no_varying(varying)
@@ -984,6 +1069,24 @@ class MaterialTable:
             h, self._flags(exact), idx, ox, oy, oz, x0.data_ptr(), x1.data_ptr(), mptr, n, int(component), int(unit),
             d[0].data_ptr(), d[1].data_ptr(), d[2].data_ptr(), p.data_ptr(), f.data_ptr(), _stream_ptr(stream)))
         return BsdfSample(d, p, f)
+
+    def sample_eval(self, out, xi, component=bsdf_flag.All, unit=unit_t.Radiance, mask=None, *, material,
+                    value=True, weight=True, stream=None, exact=None):
+        """BsdfModel.sample_eval with a material per lane (bbm_hip_sample_eval_table): lane i gets what the table's
+        sample followed by its eval_pdf at the sampled direction returns for material[i], and the weight."""
+        ox, oy, oz, n, x0, x1 = _sample_eval_inputs(out, xi)
+        h = self._live()
+        dev = x0.device
+        idx = self._material(material, n, dev)
+        mptr, _keep = _mask_ptr(mask, n)
+        outs = _sample_eval_outputs(n, dev, value, weight)
+        _on_stream(stream, _keep, material, *outs)
+        d, p, f, v, w = outs
+        _lib.check(_lib.load().bbm_hip_sample_eval_table(
+            h, self._flags(exact), idx, ox, oy, oz, x0.data_ptr(), x1.data_ptr(), mptr, n, int(component), int(unit),
+            d[0].data_ptr(), d[1].data_ptr(), d[2].data_ptr(), p.data_ptr(), f.data_ptr(), *_row_ptrs(v),
+            *_row_ptrs(w), _stream_ptr(stream)))
+        return BsdfSample(d, p, f), v, w
 
     def reflectance(self, out, component=bsdf_flag.All, unit=unit_t.Radiance, mask=None, *, material, stream=None,
                     exact=None):

@@ -312,6 +312,58 @@ int bbm_hip_sample(int model_id, const float* params, int nparams,
   return e->run.sample(a, static_cast<hipStream_t>(stream));
 }
 
+}  // extern "C"
+
+namespace {
+
+// The checks the two sample_eval calls share once the model (or table) is known, and the argument block: the
+// inputs and dir / pdf / flag are required, a value or weight group is all three pointers or none.
+int sample_eval_args(const float* out_x, const float* out_y, const float* out_z, const float* xi0, const float* xi1,
+                     const uint8_t* mask, size_t n, uint32_t component,
+                     float* dir_x, float* dir_y, float* dir_z, float* pdf, uint32_t* flag,
+                     float* r, float* g, float* b, float* wr, float* wg, float* wb, SampleEvalArgs& a)
+{
+  if (const int rc = check_dirs(out_x, out_y, out_z, "out")) return rc;
+  if (!xi0 || !xi1) return fail(BBM_HIP_ERR_INVALID_ARG, "xi pointer is NULL");
+  if (!dir_x || !dir_y || !dir_z || !pdf || !flag) return fail(BBM_HIP_ERR_INVALID_ARG, "sample output pointer is NULL");
+  if ((r || g || b) && (!r || !g || !b)) return fail(BBM_HIP_ERR_INVALID_ARG, "value output: give r, g and b or none");
+  if ((wr || wg || wb) && (!wr || !wg || !wb))
+    return fail(BBM_HIP_ERR_INVALID_ARG, "weight output: give wr, wg and wb or none");
+  std::memset(&a, 0, sizeof(a));
+  a.s.n = n;
+  a.s.ox = out_x; a.s.oy = out_y; a.s.oz = out_z; a.s.xi0 = xi0; a.s.xi1 = xi1; a.s.mask = mask;
+  a.s.dx = dir_x; a.s.dy = dir_y; a.s.dz = dir_z; a.s.pdf = pdf; a.s.flag = flag;
+  a.r = r; a.g = g; a.b = b; a.wr = wr; a.wg = wg; a.wb = wb;
+  a.s.component = component & kFlagAll;
+  return BBM_HIP_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int bbm_hip_sample_eval(int model_id, const float* params, int nparams,
+                        const float* out_x, const float* out_y, const float* out_z,
+                        const float* xi0, const float* xi1,
+                        const uint8_t* mask, size_t n, uint32_t component, uint32_t unit,
+                        float* dir_x, float* dir_y, float* dir_z, float* pdf, uint32_t* flag,
+                        float* r, float* g, float* b, float* wr, float* wg, float* wb, void* stream)
+{
+  (void)unit;
+  const CallExactScope mode_scope(model_id);
+  EvalArgs tmp;
+  const ModelEntry* e;
+  int rc = prepare(model_id, params, nparams, n, tmp, e);
+  if (rc) return rc;
+  if (n == 0) return BBM_HIP_OK;
+  SampleEvalArgs a;
+  if ((rc = sample_eval_args(out_x, out_y, out_z, xi0, xi1, mask, n, component, dir_x, dir_y, dir_z, pdf, flag,
+                             r, g, b, wr, wg, wb, a)))
+    return rc;
+  a.s.p = tmp.p;
+  return e->run.sample_eval(a, static_cast<hipStream_t>(stream));
+}
+
 int bbm_hip_reflectance(int model_id, const float* params, int nparams,
                         const float* out_x, const float* out_y, const float* out_z,
                         const uint8_t* mask, size_t n, uint32_t component, uint32_t unit,
@@ -595,6 +647,33 @@ int bbm_hip_sample_table(const bbm_hip_table* t, int call_flags, const uint32_t*
   a.e.dx = dir_x; a.e.dy = dir_y; a.e.dz = dir_z; a.e.pdf = pdf; a.e.flag = flag;
   a.e.component = component & kFlagAll;
   return t->e->run.sample_tab(a, static_cast<hipStream_t>(stream));
+}
+
+int bbm_hip_sample_eval_table(const bbm_hip_table* t, int call_flags, const uint32_t* material,
+                              const float* out_x, const float* out_y, const float* out_z,
+                              const float* xi0, const float* xi1,
+                              const uint8_t* mask, size_t n, uint32_t component, uint32_t unit,
+                              float* dir_x, float* dir_y, float* dir_z, float* pdf, uint32_t* flag,
+                              float* r, float* g, float* b, float* wr, float* wg, float* wb, void* stream)
+{
+  (void)unit;
+  int rc = table_call(t, call_flags, n, material);
+  if (rc) return rc;
+  if (!t->e->run.sample_eval_tab)
+    return fail(BBM_HIP_ERR_UNSUPPORTED, std::string(t->e->name) + ": no material-table kernels");
+  if (n == 0) return BBM_HIP_OK;
+  const CallExactScope mode_scope(call_flags);
+  SampleEvalTabArgs a;
+  std::memset(&a, 0, sizeof(a));
+  if ((rc = sample_eval_args(out_x, out_y, out_z, xi0, xi1, mask, n, component, dir_x, dir_y, dir_z, pdf, flag,
+                             r, g, b, wr, wg, wb, a.e)))
+    return rc;
+  // the block form sample and eval + pdf read (host_params applied)
+  a.e.s.p = t->first_prepared;
+  a.t.blocks = t->prepared;
+  a.t.material = material;
+  a.t.count = t->count;
+  return t->e->run.sample_eval_tab(a, static_cast<hipStream_t>(stream));
 }
 
 int bbm_hip_reflectance_table(const bbm_hip_table* t, int call_flags, const uint32_t* material,

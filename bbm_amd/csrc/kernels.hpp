@@ -1297,6 +1297,7 @@ int launch_loss(const LossArgs& a0, hipStream_t s)
 #include "image.hpp"
 #include "varying.hpp"
 #include "table.hpp"
+#include "sample_eval.hpp"
 
 namespace bbmhip {
 
@@ -1313,6 +1314,8 @@ using TablePrepare = int (*)(const ParamBlock&, bool, hipStream_t, TableBlocks&)
 using EvalTabLauncher = int (*)(const EvalTabArgs&, int, hipStream_t);
 using SampleTabLauncher = int (*)(const SampleTabArgs&, hipStream_t);
 using ReflTabLauncher = int (*)(const ReflTabArgs&, hipStream_t);
+using SampleEvalLauncher = int (*)(const SampleEvalArgs&, hipStream_t);
+using SampleEvalTabLauncher = int (*)(const SampleEvalTabArgs&, hipStream_t);
 
 // A composition's launchers: what a registry row (registry.hip) holds of its kernels.
 struct Launchers
@@ -1332,16 +1335,20 @@ struct Launchers
   EvalTabLauncher eval_pdf_tab;
   SampleTabLauncher sample_tab;
   ReflTabLauncher reflectance_tab;
+  // sample + eval + weight in one launch (sample_eval.hpp); the table twin null where there are no tables
+  SampleEvalLauncher sample_eval;
+  SampleEvalTabLauncher sample_eval_tab;
 };
 template<class M> constexpr Launchers launchers()
 {
   if constexpr (supports_varying<M>::value)
     return {&launch_eval_pdf<M>, &launch_sample<M>, &launch_reflectance<M>, &launch_loss<M>, &launch_check<M>, &launch_image<M>,
             &launch_eval_pdf_var<M>, &launch_sample_var<M>, &launch_reflectance_var<M>,
-            &table_prepare<M>, &launch_eval_pdf_tab<M>, &launch_sample_tab<M>, &launch_reflectance_tab<M>};
+            &table_prepare<M>, &launch_eval_pdf_tab<M>, &launch_sample_tab<M>, &launch_reflectance_tab<M>,
+            &launch_sample_eval<M>, &launch_sample_eval_tab<M>};
   else
     return {&launch_eval_pdf<M>, &launch_sample<M>, &launch_reflectance<M>, &launch_loss<M>, &launch_check<M>, &launch_image<M>,
-            nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+            nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &launch_sample_eval<M>, nullptr};
 }
 
 }  // namespace bbmhip

@@ -159,6 +159,42 @@ struct host_params<Aggregate<A, B>>
   static void done(void* scratch, hipStream_t s) { host_params<B>::done(scratch, s); }
 };
 
+// sample_eval (sample_eval.hpp): the kernels whose quad form has scratch at check_waves' 128 VGPRs where the row's
+// k_sample_v4 and k_eval_pdf_v4 have none; they run one lane per thread (bytes per lane in DESIGN.md §4.16).
+// D: the default-mode kernel, E: the one the exact mode launches.
+#define BBM_HIP_SAMPLE_EVAL_ONE_LANE_D(M) template<> struct sample_eval_quad<M, false> { static constexpr bool value = false; };
+#define BBM_HIP_SAMPLE_EVAL_ONE_LANE_E(M) template<> struct sample_eval_quad<M, true> { static constexpr bool value = false; };
+#define BBM_HIP_SAMPLE_EVAL_ONE_LANE(M) BBM_HIP_SAMPLE_EVAL_ONE_LANE_D(M) BBM_HIP_SAMPLE_EVAL_ONE_LANE_E(M)
+BBM_HIP_SAMPLE_EVAL_ONE_LANE_E(CookTorranceM)
+BBM_HIP_SAMPLE_EVAL_ONE_LANE_E(NganCookTorranceM)
+BBM_HIP_SAMPLE_EVAL_ONE_LANE(PhongWalterM)
+BBM_HIP_SAMPLE_EVAL_ONE_LANE(RibardiereM)
+BBM_HIP_SAMPLE_EVAL_ONE_LANE(RibardiereAnisoM)
+BBM_HIP_SAMPLE_EVAL_ONE_LANE(LowMicrofacetM)
+BBM_HIP_SAMPLE_EVAL_ONE_LANE(PhongLobe)
+BBM_HIP_SAMPLE_EVAL_ONE_LANE(LafortuneM)
+BBM_HIP_SAMPLE_EVAL_ONE_LANE(NganLafortuneM)
+BBM_HIP_SAMPLE_EVAL_ONE_LANE(ASM)
+BBM_HIP_SAMPLE_EVAL_ONE_LANE(ASFullM)
+BBM_HIP_SAMPLE_EVAL_ONE_LANE(LowASM)
+BBM_HIP_SAMPLE_EVAL_ONE_LANE(NganASM)
+BBM_HIP_SAMPLE_EVAL_ONE_LANE(Bagher)
+BBM_HIP_SAMPLE_EVAL_ONE_LANE(AggBagherM)
+BBM_HIP_SAMPLE_EVAL_ONE_LANE(AggCookTorranceM)
+BBM_HIP_SAMPLE_EVAL_ONE_LANE(AggLowASM)
+BBM_HIP_SAMPLE_EVAL_ONE_LANE(AggLowMicrofacetM)
+BBM_HIP_SAMPLE_EVAL_ONE_LANE(AggLowSmoothM)
+BBM_HIP_SAMPLE_EVAL_ONE_LANE(AggNganASM)
+BBM_HIP_SAMPLE_EVAL_ONE_LANE(AggPhongM)
+BBM_HIP_SAMPLE_EVAL_ONE_LANE(AggNganCookTorranceM)
+BBM_HIP_SAMPLE_EVAL_ONE_LANE(AggNganLafortuneM)
+// tables: EPD's 8 B are left alone, its one-lane kernel has them too
+template<> struct sample_eval_tab_quad<AggCookTorranceM, false> { static constexpr bool value = false; };
+template<> struct sample_eval_tab_quad<LowMicrofacetM, true> { static constexpr bool value = false; };
+template<> struct sample_eval_tab_quad<AggLowMicrofacetM, true> { static constexpr bool value = false; };
+template<> struct sample_eval_tab_quad<AggNganCookTorranceM, false> { static constexpr bool value = false; };
+template<> struct sample_eval_tab_quad<AggNganCookTorranceM, true> { static constexpr bool value = false; };
+
 }  // namespace bbmhip
 
 // X(composition) per instantiation unit
@@ -190,7 +226,9 @@ struct host_params<Aggregate<A, B>>
   template int table_prepare<M>(const ParamBlock&, bool, hipStream_t, TableBlocks&); \
   template int launch_eval_pdf_tab<M>(const EvalTabArgs&, int, hipStream_t);  \
   template int launch_sample_tab<M>(const SampleTabArgs&, hipStream_t);       \
-  template int launch_reflectance_tab<M>(const ReflTabArgs&, hipStream_t);
+  template int launch_reflectance_tab<M>(const ReflTabArgs&, hipStream_t);    \
+  template int launch_sample_eval<M>(const SampleEvalArgs&, hipStream_t);     \
+  template int launch_sample_eval_tab<M>(const SampleEvalTabArgs&, hipStream_t);
 #define BBM_HIP_EXTERN(M)                                                       \
   extern template int launch_eval_pdf<M>(const EvalArgs&, int, hipStream_t);    \
   extern template int launch_sample<M>(const SampleArgs&, hipStream_t);         \
@@ -204,4 +242,6 @@ struct host_params<Aggregate<A, B>>
   extern template int table_prepare<M>(const ParamBlock&, bool, hipStream_t, TableBlocks&); \
   extern template int launch_eval_pdf_tab<M>(const EvalTabArgs&, int, hipStream_t); \
   extern template int launch_sample_tab<M>(const SampleTabArgs&, hipStream_t); \
-  extern template int launch_reflectance_tab<M>(const ReflTabArgs&, hipStream_t);
+  extern template int launch_reflectance_tab<M>(const ReflTabArgs&, hipStream_t); \
+  extern template int launch_sample_eval<M>(const SampleEvalArgs&, hipStream_t); \
+  extern template int launch_sample_eval_tab<M>(const SampleEvalTabArgs&, hipStream_t);

@@ -1,0 +1,323 @@
+// bbm_amd/csrc/sample_eval.hpp -- one BSDF call per bounce in one launch: draw a direction for `out`, evaluate the
+// model at (dir, out) and form the path's throughput weight eval . cos / pdf (bbm_hip_sample_eval and its material
+// table twin bbm_hip_sample_eval_table).  Included at the end of kernels.hpp, after table.hpp.
+//
+// Lane i returns what the staged pair of calls returns for it, bit for bit: dir / pdf / flag are bbm_hip_sample's,
+// value is the r, g, b of bbm_hip_eval_pdf (both outputs) at in = dir, and weight[c] is
+// pdf > epsilon ? (value[c] * dir.z) / pdf : 0, the term of checkBsdf's reflectance test (k_check, kEpsF) with the
+// IEEE float quotient (sample_weight).  Nothing is special-cased: a lane whose sample failed (flag 0, zero direction), a lane below the
+// horizon and a masked lane evaluate the model at whatever direction the sampler returned, as the staged calls do.
+// The sampled direction never leaves the registers, which is the point: 52 or 64 B per lane instead of 76.
+//
+// Layout: k_sample_v4's -- four consecutive lanes per thread-iteration, five 16-byte loads and one 16-byte store per
+// output array, grid-stride up to max_blocks(), a scalar tail.  The mask and whether the value and the weight group
+// are stored are runtime, wave-uniform arguments, so a row has one quad and one one-lane kernel, times the exact
+// variant where it has one.  Unaligned arrays (and the rows sample_eval_quad excludes) take one lane per thread.
+#pragma once
+
+namespace bbmhip {
+
+struct SampleEvalArgs
+{
+  SampleArgs s;                       // the inputs, and dir / pdf / flag (required)
+  float* r; float* g; float* b;       // value = eval(dir, out); all null: not stored
+  float* wr; float* wg; float* wb;    // weight; all null: not stored
+};
+struct SampleEvalTabArgs { SampleEvalArgs e; TabRef t; };     // e.s.p: the fallback block (table.hpp)
+
+template<class Model> constexpr bool fused_sample_eval()
+{
+  if constexpr (requires { Model::kFusedSampleEval; }) return Model::kFusedSampleEval;
+  else return false;
+}
+
+// sample(out, xi) and eval(dir, out) of one lane.  Default mode: the model's own sample_eval where it has one (the
+// microfacet models: one halfway vector and one D for both, bit-identical to the separate calls).  Exact mode
+// (EXACT, a model with model_has_exact; m is then the sampler's exact twin): the sampler takes its pdf from the
+// default evaluation while the staged eval runs the exact one, so the two are called one after the other -- one fused
+// exact eval_pdf would return the exact pdf, which is not bbm_hip_sample's in the subnormal lanes.
+template<bool EXACT, class Model>
+__device__ __forceinline__ void model_sample_eval(const Model& m, v3 out, float xi0, float xi1, uint32_t comp,
+                                                  v3& dir, float* rgb, float& pdf, uint32_t& flag)
+{
+  if constexpr (!EXACT && fused_sample_eval<Model>()) m.sample_eval(out, xi0, xi1, comp, dir, rgb, pdf, flag);
+  else
+  {
+    float unused;
+    m.sample(out, xi0, xi1, comp, dir, pdf, flag);
+    model_eval_pdf<kModeEval, EXACT>(m, dir, out, comp, rgb, unused);
+  }
+}
+
+// checkBsdf's importance-sampling term (checkBsdf.cpp:85-86; k_check, kCheckReflectance), per lane.  The quotient is
+// the IEEE float division, as the reference's: k_check forms it with div_nr, which is that quotient except within
+// ~2^-22 ulp of a rounding midpoint and -- seen on the GPU, DESIGN.md §4.16 -- where the remainder n - d q of a tiny
+// normal quotient is itself subnormal (Bagher: 1.3805531e-37 for 1.3805532e-37).  Three divisions per lane of a
+// kernel that moves 52-64 B per lane are not its bound.
+__device__ __forceinline__ void sample_weight(const float* rgb, float dz, float pdf, float* w)
+{
+#pragma unroll
+  for (int c = 0; c < 3; ++c) w[c] = (pdf > kEpsF) ? (rgb[c] * dz) / pdf : 0.0f;
+}
+
+template<bool EXACT, class Model>
+__device__ __forceinline__ void one_sample_eval(const Model& m, const SampleEvalArgs& a, uint64_t i, bool active)
+{
+  const SampleArgs& s = a.s;
+  v3 d; float rgb[3], pdf; uint32_t f;
+  model_sample_eval<EXACT>(m, mk3(s.ox[i], s.oy[i], s.oz[i]), s.xi0[i], s.xi1[i], active ? s.component : 0u, d, rgb,
+                           pdf, f);
+  s.dx[i] = d.x; s.dy[i] = d.y; s.dz[i] = d.z; s.pdf[i] = pdf; s.flag[i] = f;
+  if (a.r) { a.r[i] = rgb[0]; a.g[i] = rgb[1]; a.b[i] = rgb[2]; }
+  if (a.wr)
+  {
+    float w[3];
+    sample_weight(rgb, d.z, pdf, w);
+    a.wr[i] = w[0]; a.wg[i] = w[1]; a.wb[i] = w[2];
+  }
+}
+
+// Whether the quad form is used for aligned arrays, per mode (EXACT: the kernel the exact mode launches).  From the
+// compiler's resource report: a row whose quad form has scratch where neither its k_sample_v4 nor
+// its k_eval_pdf_v4 has runs one lane per thread, which for all of them needs none or less.  The uniform and the
+// table kernel are judged on their own (the table's has no grid-stride loop and holds fewer registers).
+// Specialised in models.hpp.
+template<class Model, bool EXACT> struct sample_eval_quad { static constexpr bool value = true; };
+template<class Model, bool EXACT> struct sample_eval_tab_quad { static constexpr bool value = true; };
+
+// Occupancy: the chain is k_check's reflectance test (sample, eval, the weight), so its choice is the starting point
+// (check_waves: 4 waves per SIMD, the compiler's own for the He family and EPD) -- not measured for this kernel.
+#define BBM_HIP_SAMPLE_EVAL_ATTR(Model) __attribute__((amdgpu_waves_per_eu(check_waves<Model>::value, 8)))
+
+// One quad's stores, t the quad's index in every array; the weights are formed only where they are stored.
+__device__ __forceinline__ void store_sample_eval(const SampleEvalArgs& a, uint64_t t, const float* dx,
+                                                  const float* dy, const float* dz, const float* pd,
+                                                  const uint32_t* fl, const float (*rgb)[4])
+{
+  const SampleArgs& s = a.s;
+  st4<true>(s.dx, t, dx[0], dx[1], dx[2], dx[3]);
+  st4<true>(s.dy, t, dy[0], dy[1], dy[2], dy[3]);
+  st4<true>(s.dz, t, dz[0], dz[1], dz[2], dz[3]);
+  st4<true>(s.pdf, t, pd[0], pd[1], pd[2], pd[3]);
+  typedef uint32_t u4 __attribute__((ext_vector_type(4)));
+  __builtin_nontemporal_store(u4{fl[0], fl[1], fl[2], fl[3]}, reinterpret_cast<u4*>(s.flag) + t);
+  if (a.r)
+  {
+    st4<true>(a.r, t, rgb[0][0], rgb[0][1], rgb[0][2], rgb[0][3]);
+    st4<true>(a.g, t, rgb[1][0], rgb[1][1], rgb[1][2], rgb[1][3]);
+    st4<true>(a.b, t, rgb[2][0], rgb[2][1], rgb[2][2], rgb[2][3]);
+  }
+  if (a.wr)
+  {
+    float w[3][4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+    {
+      const float f[3] = {rgb[0][j], rgb[1][j], rgb[2][j]};
+      float wj[3];
+      sample_weight(f, dz[j], pd[j], wj);
+      w[0][j] = wj[0]; w[1][j] = wj[1]; w[2][j] = wj[2];
+    }
+    st4<true>(a.wr, t, w[0][0], w[0][1], w[0][2], w[0][3]);
+    st4<true>(a.wg, t, w[1][0], w[1][1], w[1][2], w[1][3]);
+    st4<true>(a.wb, t, w[2][0], w[2][1], w[2][2], w[2][3]);
+  }
+}
+
+// 4 lanes per thread-iteration: 5 x 16-byte loads (out xyz, xi0, xi1), 5 + 3 + 3 x 16-byte stores.  Requires every
+// array 16-byte aligned and the mask 4-byte aligned (checked on the host); the n % 4 tail runs scalar.
+template<class Model, bool EXACT>
+__global__ __launch_bounds__(kBlock) BBM_HIP_SAMPLE_EVAL_ATTR(Model) void k_sample_eval_v4(SampleEvalArgs a)
+{
+  math_tables_init();
+  const Model m(a.s.p.v);
+  const SampleArgs& s = a.s;
+  const uint64_t n4 = s.n >> 2;
+  const uint64_t stride = uint64_t(gridDim.x) * kBlock;
+  for (uint64_t t = uint64_t(blockIdx.x) * kBlock + threadIdx.x; t < n4; t += stride)
+  {
+    const float4 ox = ld4<true>(s.ox, t), oy = ld4<true>(s.oy, t), oz = ld4<true>(s.oz, t);
+    const float4 x0 = ld4<true>(s.xi0, t), x1 = ld4<true>(s.xi1, t);
+    const uint32_t mk = s.mask ? reinterpret_cast<const uint32_t*>(s.mask)[t] : 0x01010101u;
+    const float onx[4] = {ox.x, ox.y, ox.z, ox.w}, ony[4] = {oy.x, oy.y, oy.z, oy.w}, onz[4] = {oz.x, oz.y, oz.z, oz.w};
+    const float u0[4] = {x0.x, x0.y, x0.z, x0.w}, u1[4] = {x1.x, x1.y, x1.z, x1.w};
+    float dx[4], dy[4], dz[4], pd[4], rgb[3][4];
+    uint32_t fl[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+    {
+      v3 d;
+      float f[3];
+      const uint32_t comp = ((mk >> (8 * j)) & 0xffu) ? s.component : 0u;
+      model_sample_eval<EXACT>(m, mk3(onx[j], ony[j], onz[j]), u0[j], u1[j], comp, d, f, pd[j], fl[j]);
+      dx[j] = d.x; dy[j] = d.y; dz[j] = d.z;
+#pragma unroll
+      for (int c = 0; c < 3; ++c) rgb[c][j] = f[c];
+    }
+    store_sample_eval(a, t, dx, dy, dz, pd, fl, rgb);
+  }
+  if (blockIdx.x == 0 && threadIdx.x < (s.n & 3))
+  {
+    const uint64_t i = (n4 << 2) + threadIdx.x;
+    one_sample_eval<EXACT>(m, a, i, s.mask ? (s.mask[i] != 0) : true);
+  }
+}
+
+// Scalar path for unaligned arrays.
+template<class Model, bool EXACT>
+__global__ __launch_bounds__(kBlock) BBM_HIP_SAMPLE_EVAL_ATTR(Model) void k_sample_eval_v1(SampleEvalArgs a)
+{
+  math_tables_init();
+  const Model m(a.s.p.v);
+  const uint64_t stride = uint64_t(gridDim.x) * kBlock;
+  for (uint64_t i = uint64_t(blockIdx.x) * kBlock + threadIdx.x; i < a.s.n; i += stride)
+    one_sample_eval<EXACT>(m, a, i, a.s.mask ? (a.s.mask[i] != 0) : true);
+}
+
+// Material tables: the same lane behind table.hpp's block gather and index load.  S: the slot count of the model the
+// table was made for (Model may be its exact-mode sampling twin).  One model is live at a time.
+template<class Model, int S, bool EXACT>
+__device__ __forceinline__ void tab_one_sample_eval(const SampleEvalTabArgs& a, uint64_t i)
+{
+  const SampleArgs& s = a.e.s;
+  const uint32_t id = a.t.material[i];
+  ParamBlock q;
+  tab_block<S>(s.p, a.t, id, q);
+  const Model m(q.v);
+  one_sample_eval<EXACT>(m, a.e, i, (s.mask ? (s.mask[i] != 0) : true) && id < a.t.count);
+}
+
+// Four lanes per thread; every float array and the index array 16-byte aligned, the mask 4-byte aligned.  A full
+// grid, as the other table kernels.
+template<class Model, int S, bool EXACT>
+__global__ __launch_bounds__(kBlock) BBM_HIP_SAMPLE_EVAL_ATTR(Model) void k_sample_eval_tab(SampleEvalTabArgs a)
+{
+  math_tables_init();
+  const SampleArgs& s = a.e.s;
+  const uint64_t n4 = s.n >> 2;
+  const uint64_t t = uint64_t(blockIdx.x) * kBlock + threadIdx.x;
+  if (t < n4)
+  {
+    const float4 ox = ld4<true>(s.ox, t), oy = ld4<true>(s.oy, t), oz = ld4<true>(s.oz, t);
+    const float4 x0 = ld4<true>(s.xi0, t), x1 = ld4<true>(s.xi1, t);
+    typedef uint32_t u4 __attribute__((ext_vector_type(4)));
+    const u4 idv = __builtin_nontemporal_load(reinterpret_cast<const u4*>(a.t.material) + t);
+    const uint32_t mk = s.mask ? reinterpret_cast<const uint32_t*>(s.mask)[t] : 0x01010101u;
+    const uint32_t id[4] = {idv.x, idv.y, idv.z, idv.w};
+    const float onx[4] = {ox.x, ox.y, ox.z, ox.w}, ony[4] = {oy.x, oy.y, oy.z, oy.w}, onz[4] = {oz.x, oz.y, oz.z, oz.w};
+    const float u0[4] = {x0.x, x0.y, x0.z, x0.w}, u1[4] = {x1.x, x1.y, x1.z, x1.w};
+    float dx[4], dy[4], dz[4], pd[4], rgb[3][4];
+    uint32_t fl[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+    {
+      ParamBlock q;
+      tab_block<S>(s.p, a.t, id[j], q);
+      const Model m(q.v);
+      v3 d;
+      float f[3];
+      const uint32_t comp = (((mk >> (8 * j)) & 0xffu) && id[j] < a.t.count) ? s.component : 0u;
+      model_sample_eval<EXACT>(m, mk3(onx[j], ony[j], onz[j]), u0[j], u1[j], comp, d, f, pd[j], fl[j]);
+      dx[j] = d.x; dy[j] = d.y; dz[j] = d.z;
+#pragma unroll
+      for (int c = 0; c < 3; ++c) rgb[c][j] = f[c];
+    }
+    store_sample_eval(a.e, t, dx, dy, dz, pd, fl, rgb);
+  }
+  // tail
+  if (blockIdx.x == 0 && threadIdx.x < (s.n & 3)) tab_one_sample_eval<Model, S, EXACT>(a, (n4 << 2) + threadIdx.x);
+}
+
+// One lane per thread: unaligned arrays (and the rows sample_eval_tab_quad excludes).
+template<class Model, int S, bool EXACT>
+__global__ __launch_bounds__(kBlock) BBM_HIP_SAMPLE_EVAL_ATTR(Model) void k_sample_eval_tab1(SampleEvalTabArgs a)
+{
+  math_tables_init();
+  const uint64_t i = uint64_t(blockIdx.x) * kBlock + threadIdx.x;
+  if (i < a.e.s.n) tab_one_sample_eval<Model, S, EXACT>(a, i);
+}
+
+inline bool sample_eval_aligned(const SampleEvalArgs& a)
+{
+  const SampleArgs& s = a.s;
+  return aligned16(s.ox) && aligned16(s.oy) && aligned16(s.oz) && aligned16(s.xi0) && aligned16(s.xi1) &&
+         aligned16(s.dx) && aligned16(s.dy) && aligned16(s.dz) && aligned16(s.pdf) && aligned16(s.flag) &&
+         aligned16(a.r) && aligned16(a.g) && aligned16(a.b) && aligned16(a.wr) && aligned16(a.wg) &&
+         aligned16(a.wb) && (reinterpret_cast<uintptr_t>(s.mask) & 3u) == 0;
+}
+
+// What the exact mode launches for a row: the sampler's twin where it has one (launch_sample_mask), evaluated with
+// the exact eval_pdf where the model has one (launch_mode) -- the two staged calls' choices, each on its own.
+template<class Model> constexpr bool sample_eval_has_exact() { return has_exact_sample<Model>() || model_has_exact<Model>(); }
+
+// One mode's launch: K the kernels' model type (the row's, or its sampler's exact twin), QUAD the mode's trait.
+template<class K, bool E, bool QUAD>
+void launch_sample_eval_kernel(const SampleEvalArgs& a, hipStream_t s)
+{
+  const bool vec = QUAD && sample_eval_aligned(a);
+  const uint64_t units = vec ? (a.s.n >> 2) : a.s.n;
+  uint64_t blocks = (units + kBlock - 1) / kBlock;
+  if (blocks < 1) blocks = 1;
+  if (blocks > max_blocks()) blocks = max_blocks();
+  if constexpr (QUAD)
+  {
+    if (vec) hipLaunchKernelGGL((k_sample_eval_v4<K, E>), dim3(unsigned(blocks)), dim3(kBlock), 0, s, a);
+  }
+  if (!vec) hipLaunchKernelGGL((k_sample_eval_v1<K, E>), dim3(unsigned(blocks)), dim3(kBlock), 0, s, a);
+}
+
+template<class Model>
+int launch_sample_eval(const SampleEvalArgs& a0, hipStream_t s)
+{
+  if (const int rc = host_prepare<Model>::run(s)) return rc;
+  if (const int rc = host_validate<Model>::run(a0.s.p)) return rc;
+  SampleEvalArgs a = a0;
+  void* scratch = nullptr;
+  if (const int rc = host_params<Model>::run(a.s.p, a.s.component, s, &scratch)) return rc;
+  struct Release { void* p; hipStream_t s; ~Release() { host_params<Model>::done(p, s); } } release{scratch, s};
+  bool exact = false;
+  if constexpr (sample_eval_has_exact<Model>())
+    if (exact_on())
+    {
+      launch_sample_eval_kernel<exact_sample_t<Model>, model_has_exact<Model>(), sample_eval_quad<Model, true>::value>(a, s);
+      exact = true;
+    }
+  if (!exact) launch_sample_eval_kernel<Model, false, sample_eval_quad<Model, false>::value>(a, s);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fail(BBM_HIP_ERR_HIP, std::string("kernel launch failed: ") + hipGetErrorString(e));
+  return BBM_HIP_OK;
+}
+
+// a full grid, as the other table kernels; 0 where the batch is too large for one launch (var_blocks)
+template<class K, int S, bool E, bool QUAD>
+unsigned launch_sample_eval_tab_kernel(const SampleEvalTabArgs& a, hipStream_t s)
+{
+  const bool vec = QUAD && sample_eval_aligned(a.e) && aligned16(a.t.material);
+  const unsigned blocks = var_blocks(vec ? (a.e.s.n >> 2) : a.e.s.n);
+  if (blocks == 0) return blocks;
+  if constexpr (QUAD)
+  {
+    if (vec) hipLaunchKernelGGL((k_sample_eval_tab<K, S, E>), dim3(blocks), dim3(kBlock), 0, s, a);
+  }
+  if (!vec) hipLaunchKernelGGL((k_sample_eval_tab1<K, S, E>), dim3(blocks), dim3(kBlock), 0, s, a);
+  return blocks;
+}
+
+// The table's blocks were prepared at create (table_prepare: host_prepare, host_validate, host_params per material),
+// so, as launch_sample_tab, nothing is left to do on the host but choose the kernel.
+template<class Model>
+int launch_sample_eval_tab(const SampleEvalTabArgs& a, hipStream_t s)
+{
+  if constexpr (!supports_varying<Model>::value) return var_unsupported();
+  else
+  {
+    constexpr int S = table_slots<Model>::value;
+    if constexpr (sample_eval_has_exact<Model>())
+      if (exact_on())
+        return var_launched(launch_sample_eval_tab_kernel<exact_sample_t<Model>, S, model_has_exact<Model>(),
+                                                          sample_eval_tab_quad<Model, true>::value>(a, s));
+    return var_launched(launch_sample_eval_tab_kernel<Model, S, false, sample_eval_tab_quad<Model, false>::value>(a, s));
+  }
+}
+
+}  // namespace bbmhip

@@ -133,6 +133,30 @@ int bbm_hip_sample(int model_id, const float* params, int nparams,
                    float* dir_x, float* dir_y, float* dir_z, float* pdf, uint32_t* flag,
                    void* stream);
 
+/* One BSDF call per bounce in one launch: sample, then eval at the sampled direction, then the path's throughput
+ * weight (what a renderer's sample() returns: the reference's Mitsuba plugin per shading point, checkBsdf's
+ * importance-sampled reflectance per draw, bin/checkBsdf.cpp:82-86).  For lane i:
+ *   dir, pdf, flag  bit for bit what bbm_hip_sample returns (same id, parameters, component, mask and mode);
+ *   value (r, g, b) bit for bit the r, g, b of bbm_hip_eval_pdf (both outputs) at in = dir, out = out -- on every
+ *                   lane: a failed sample (flag 0, zero direction), a lane below the horizon, xi outside [0, 1] and a
+ *                   masked lane return whatever the staged pair of calls returns there;
+ *   weight[c]       pdf > epsilon(float) ? (value[c] * dir_z) / pdf : 0 in IEEE float arithmetic, the term of
+ *                   checkBsdf's reflectance test (no claim is made for Mitsuba's Spectrum / Float rounding).
+ * The sampled direction stays in registers: 52 B per lane with the weight alone, 64 B with value and weight, against
+ * 76 B for bbm_hip_sample followed by bbm_hip_eval.  dir / pdf / flag are required; value and weight are each stored
+ * only if all three of their pointers are given, and a group with one or two pointers is BBM_HIP_ERR_INVALID_ARG.
+ * BBM_HIP_RUNTIME_AGGREGATE and BBM_HIP_CALL_EXACT / _DEFAULT select what they select in the two staged calls (the
+ * sampler's exact twin and the exact evaluation, each where the model has one).  Errors come before any launch, in
+ * the order of every per-model call: the id, the parameter count, NULL pointers; n == 0 is a no-op.  floatRGB only. */
+int bbm_hip_sample_eval(int model_id, const float* params, int nparams,
+                        const float* out_x, const float* out_y, const float* out_z,
+                        const float* xi0, const float* xi1,
+                        const uint8_t* mask, size_t n, uint32_t component, uint32_t unit,
+                        float* dir_x, float* dir_y, float* dir_z, float* pdf, uint32_t* flag,
+                        float* r, float* g, float* b,        /* value  = eval(dir, out); all three NULL: not stored */
+                        float* wr, float* wg, float* wb,     /* weight; all three NULL: not stored */
+                        void* stream);
+
 /* reflectance (RGB) for n outgoing directions -- bsdfmodel::reflectance, the (approximate)
  * hemispherical reflectance, e.g. bsdfmodel/microfacet.h:182-196, lambertian.h:136-140; the
  * weights aggregatemodel uses to mix its children's pdfs (aggregatemodel.h:81-150). */
@@ -216,6 +240,14 @@ int bbm_hip_sample_table(const bbm_hip_table* table, int call_flags, const uint3
                          const float* xi0, const float* xi1,
                          const uint8_t* mask, size_t n, uint32_t component, uint32_t unit,
                          float* dir_x, float* dir_y, float* dir_z, float* pdf, uint32_t* flag, void* stream);
+/* bbm_hip_sample_eval per material: lane i returns what bbm_hip_sample_table followed by bbm_hip_eval_pdf_table
+ * (both outputs) at in = dir returns, and the weight of bbm_hip_sample_eval; the output groups as there. */
+int bbm_hip_sample_eval_table(const bbm_hip_table* table, int call_flags, const uint32_t* material,
+                              const float* out_x, const float* out_y, const float* out_z,
+                              const float* xi0, const float* xi1,
+                              const uint8_t* mask, size_t n, uint32_t component, uint32_t unit,
+                              float* dir_x, float* dir_y, float* dir_z, float* pdf, uint32_t* flag,
+                              float* r, float* g, float* b, float* wr, float* wg, float* wb, void* stream);
 int bbm_hip_reflectance_table(const bbm_hip_table* table, int call_flags, const uint32_t* material,
                               const float* out_x, const float* out_y, const float* out_z,
                               const uint8_t* mask, size_t n, uint32_t component, uint32_t unit,
