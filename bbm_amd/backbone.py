@@ -151,12 +151,54 @@ def _sample_eval_inputs(out, xi):
     return ox, oy, oz, n, x0, x1
 
 
+def _device(t):
+    """The device of a (3, N) tensor or of a tuple of rows."""
+    return (t[0] if isinstance(t, (tuple, list)) else t).device
+
+
+def _xi_rows(xi, n, dtype):
+    """sample's two xi rows of `dtype`, from a (2, N) tensor or a pair of rows, one entry per direction."""
+    if isinstance(xi, (tuple, list)):
+        x0, x1 = xi
+    else:
+        if xi.dim() != 2 or xi.shape[0] != 2:
+            raise ValueError("xi: expected a (2, N) tensor")
+        x0, x1 = xi[0], xi[1]
+    for x in (x0, x1):
+        if x.dtype != dtype or not x.is_cuda or x.numel() != n or x.stride(0) != 1:
+            raise TypeError(f"xi: expected {str(dtype).replace('torch.', '')} CUDA rows with one entry per direction")
+    return x0, x1
+
+
+def _eval_pdf_outputs(mode, n, device, rgb, pdf):
+    """eval_pdf's (rgb, pdf) for the outputs `mode` asks for (1: rgb, 2: pdf): allocated, or the caller's buffer
+    validated; an output that is not asked for is passed through."""
+    torch = _torch()
+    if mode & 1:
+        rgb = torch.empty((3, n), dtype=torch.float32, device=device) if rgb is None else \
+            _out_rows(rgb, 3, n, device, "rgb")
+    if mode & 2:
+        pdf = torch.empty((n,), dtype=torch.float32, device=device) if pdf is None else \
+            _out_rows(pdf, 0, n, device, "pdf")
+    return rgb, pdf
+
+
+def _eval_pdf_ptrs(mode, rgb, pdf):
+    """The r, g, b and pdf pointers of the calls that take the mode from their outputs: NULL where not asked for."""
+    return (*_row_ptrs(rgb if mode & 1 else None), pdf.data_ptr() if mode & 2 else None)
+
+
+def _sample_outputs(n, device, dtype):
+    """(direction, pdf, flag) for one sample call."""
+    torch = _torch()
+    return (torch.empty((3, n), dtype=dtype, device=device), torch.empty((n,), dtype=dtype, device=device),
+            torch.empty((n,), dtype=torch.int32, device=device))
+
+
 def _sample_eval_outputs(n, device, value, weight):
     """(direction, pdf, flag, value or None, weight or None) for one sample_eval call."""
     torch = _torch()
-    d = torch.empty((3, n), dtype=torch.float32, device=device)
-    p = torch.empty((n,), dtype=torch.float32, device=device)
-    f = torch.empty((n,), dtype=torch.int32, device=device)
+    d, p, f = _sample_outputs(n, device, torch.float32)
     v = torch.empty((3, n), dtype=torch.float32, device=device) if value else None
     w = torch.empty((3, n), dtype=torch.float32, device=device) if weight else None
     return d, p, f, v, w
@@ -419,23 +461,17 @@ class BsdfModel:
         ox, oy, oz, _ = _soa(out, n, what="out")
         mptr, _keep = _mask_ptr(mask, n)
         dev = torch.device("cuda", torch.cuda.current_device())
-        if mode & 1:
-            rgb = torch.empty((3, n), dtype=torch.float32, device=dev) if rgb is None else \
-                _out_rows(rgb, 3, n, dev, "rgb")
-        if mode & 2:
-            pdf = torch.empty((n,), dtype=torch.float32, device=dev) if pdf is None else \
-                _out_rows(pdf, 0, n, dev, "pdf")
+        rgb, pdf = _eval_pdf_outputs(mode, n, dev, rgb, pdf)
         lib = _lib.load()
         s = _stream_ptr(stream)
         _on_stream(stream, _keep, rgb, pdf)
         mid = self._call_id(exact)
         if varying is not None:
-            vptr, vrows = self._varying(varying, n, (in_[0] if isinstance(in_, (tuple, list)) else in_).device)
+            vptr, vrows = self._varying(varying, n, _device(in_))
             _on_stream(stream, *vrows)
             _lib.check(lib.bbm_hip_eval_pdf_varying(
                 mid, self._pptr(), self._params.size, vptr, ix, iy, iz, ox, oy, oz, mptr, n, int(component), int(unit),
-                rgb[0].data_ptr() if mode & 1 else None, rgb[1].data_ptr() if mode & 1 else None,
-                rgb[2].data_ptr() if mode & 1 else None, pdf.data_ptr() if mode & 2 else None, s))
+                *_eval_pdf_ptrs(mode, rgb, pdf), s))
             return rgb, pdf
         if mode == 3:
             rc = lib.bbm_hip_eval_pdf(mid, self._pptr(), self._params.size, ix, iy, iz, ox, oy, oz, mptr, n,
@@ -466,20 +502,10 @@ class BsdfModel:
         f64 = _is_f64(out)
         dt = torch.float64 if f64 else torch.float32
         ox, oy, oz, n = _soa(out, what="out", dtype=dt)
-        if isinstance(xi, (tuple, list)):
-            x0, x1 = xi
-        else:
-            if xi.dim() != 2 or xi.shape[0] != 2:
-                raise ValueError("xi: expected a (2, N) tensor")
-            x0, x1 = xi[0], xi[1]
-        for x in (x0, x1):
-            if x.dtype != dt or not x.is_cuda or x.numel() != n or x.stride(0) != 1:
-                raise TypeError(f"xi: expected {str(dt).replace('torch.', '')} CUDA rows with one entry per direction")
+        x0, x1 = _xi_rows(xi, n, dt)
         mptr, _keep = _mask_ptr(mask, n)
         dev = x0.device
-        d = torch.empty((3, n), dtype=dt, device=dev)
-        p = torch.empty((n,), dtype=dt, device=dev)
-        f = torch.empty((n,), dtype=torch.int32, device=dev)
+        d, p, f = _sample_outputs(n, dev, dt)
         _on_stream(stream, _keep, d, p, f)
         lib = _lib.load()
         if varying is not None:
@@ -528,7 +554,7 @@ class BsdfModel:
         if _is_f64(out):
             ox, oy, oz, n = _soa(out, what="out", dtype=torch.float64)
             mptr, _keep = _mask_ptr(mask, n)
-            dev = (out[0] if isinstance(out, (tuple, list)) else out).device
+            dev = _device(out)
             rgb = torch.empty((3, n), dtype=torch.float64, device=dev)
             p = self._params_f64(params64)
             _on_stream(stream, _keep, rgb)
@@ -538,7 +564,7 @@ class BsdfModel:
             return rgb
         ox, oy, oz, n = _soa(out, what="out")
         mptr, _keep = _mask_ptr(mask, n)
-        dev = (out[0] if isinstance(out, (tuple, list)) else out).device
+        dev = _device(out)
         rgb = torch.empty((3, n), dtype=torch.float32, device=dev)
         _on_stream(stream, _keep, rgb)
         lib = _lib.load()
@@ -1014,26 +1040,19 @@ class MaterialTable:
 
     def eval_pdf(self, in_, out, component=bsdf_flag.All, unit=unit_t.Radiance, mask=None, *, material,
                  rgb=None, pdf=None, stream=None, mode=3, exact=None):
-        torch = _torch()
         if _is_f64(in_) or _is_f64(out):
             raise TypeError("MaterialTable: material tables are floatRGB only (float32 tensors)")
         h = self._live()
         ix, iy, iz, n = _soa(in_, what="in")
         ox, oy, oz, _ = _soa(out, n, what="out")
-        dev = (in_[0] if isinstance(in_, (tuple, list)) else in_).device
+        dev = _device(in_)
         idx = self._material(material, n, dev)
         mptr, _keep = _mask_ptr(mask, n)
-        if mode & 1:
-            rgb = torch.empty((3, n), dtype=torch.float32, device=dev) if rgb is None else \
-                _out_rows(rgb, 3, n, dev, "rgb")
-        if mode & 2:
-            pdf = torch.empty((n,), dtype=torch.float32, device=dev) if pdf is None else \
-                _out_rows(pdf, 0, n, dev, "pdf")
+        rgb, pdf = _eval_pdf_outputs(mode, n, dev, rgb, pdf)
         _on_stream(stream, _keep, rgb, pdf, material)
         _lib.check(_lib.load().bbm_hip_eval_pdf_table(
             h, self._flags(exact), idx, ix, iy, iz, ox, oy, oz, mptr, n, int(component), int(unit),
-            rgb[0].data_ptr() if mode & 1 else None, rgb[1].data_ptr() if mode & 1 else None,
-            rgb[2].data_ptr() if mode & 1 else None, pdf.data_ptr() if mode & 2 else None, _stream_ptr(stream)))
+            *_eval_pdf_ptrs(mode, rgb, pdf), _stream_ptr(stream)))
         return rgb, pdf
 
     def eval(self, in_, out, component=bsdf_flag.All, unit=unit_t.Radiance, mask=None, **kw):
@@ -1049,21 +1068,11 @@ class MaterialTable:
             raise TypeError("MaterialTable: material tables are floatRGB only (float32 tensors)")
         h = self._live()
         ox, oy, oz, n = _soa(out, what="out")
-        if isinstance(xi, (tuple, list)):
-            x0, x1 = xi
-        else:
-            if xi.dim() != 2 or xi.shape[0] != 2:
-                raise ValueError("xi: expected a (2, N) tensor")
-            x0, x1 = xi[0], xi[1]
-        for x in (x0, x1):
-            if x.dtype != torch.float32 or not x.is_cuda or x.numel() != n or x.stride(0) != 1:
-                raise TypeError("xi: expected float32 CUDA rows with one entry per direction")
+        x0, x1 = _xi_rows(xi, n, torch.float32)
         dev = x0.device
         idx = self._material(material, n, dev)
         mptr, _keep = _mask_ptr(mask, n)
-        d = torch.empty((3, n), dtype=torch.float32, device=dev)
-        p = torch.empty((n,), dtype=torch.float32, device=dev)
-        f = torch.empty((n,), dtype=torch.int32, device=dev)
+        d, p, f = _sample_outputs(n, dev, torch.float32)
         _on_stream(stream, _keep, d, p, f, material)
         _lib.check(_lib.load().bbm_hip_sample_table(
             h, self._flags(exact), idx, ox, oy, oz, x0.data_ptr(), x1.data_ptr(), mptr, n, int(component), int(unit),
@@ -1095,7 +1104,7 @@ class MaterialTable:
             raise TypeError("MaterialTable: material tables are floatRGB only (float32 tensors)")
         h = self._live()
         ox, oy, oz, n = _soa(out, what="out")
-        dev = (out[0] if isinstance(out, (tuple, list)) else out).device
+        dev = _device(out)
         idx = self._material(material, n, dev)
         mptr, _keep = _mask_ptr(mask, n)
         rgb = torch.empty((3, n), dtype=torch.float32, device=dev)

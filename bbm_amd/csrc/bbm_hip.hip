@@ -225,6 +225,83 @@ __global__ __launch_bounds__(kBlock) void k_libm(int func, const float* a, const
 
 using namespace bbmhip;
 
+namespace {
+
+// The pointer checks a family of entry points shares once the model (or table) is known, and the argument block
+// filled from them; the parameter block `p` is the caller's to set.
+
+// mode: the uniform calls' explicit mode, whose outputs are then required; 0 from the varying and table calls, which
+// take it from the outputs that are not NULL.
+int eval_args(int& mode, const float* in_x, const float* in_y, const float* in_z,
+              const float* out_x, const float* out_y, const float* out_z, const uint8_t* mask, size_t n,
+              uint32_t component, float* r, float* g, float* b, float* pdf, EvalArgs& a)
+{
+  int rc;
+  if ((rc = check_dirs(in_x, in_y, in_z, "in")) || (rc = check_dirs(out_x, out_y, out_z, "out"))) return rc;
+  if (mode)
+  {
+    if ((mode & kModeEval) && (!r || !g || !b)) return fail(BBM_HIP_ERR_INVALID_ARG, "eval output pointer is NULL");
+    if ((mode & kModePdf) && !pdf) return fail(BBM_HIP_ERR_INVALID_ARG, "pdf output pointer is NULL");
+  }
+  else
+  {
+    const bool want_eval = r || g || b;
+    if (want_eval && (!r || !g || !b)) return fail(BBM_HIP_ERR_INVALID_ARG, "eval output pointer is NULL");
+    if (!want_eval && !pdf) return fail(BBM_HIP_ERR_INVALID_ARG, "every output pointer is NULL");
+    mode = (want_eval ? kModeEval : 0) | (pdf ? kModePdf : 0);
+  }
+  std::memset(&a, 0, sizeof(a));
+  a.n = n;
+  a.ix = in_x; a.iy = in_y; a.iz = in_z; a.ox = out_x; a.oy = out_y; a.oz = out_z;
+  a.mask = mask; a.r = r; a.g = g; a.b = b; a.pdf = pdf;
+  a.component = component & kFlagAll;
+  return BBM_HIP_OK;
+}
+
+int sample_args(const float* out_x, const float* out_y, const float* out_z, const float* xi0, const float* xi1,
+                const uint8_t* mask, size_t n, uint32_t component,
+                float* dir_x, float* dir_y, float* dir_z, float* pdf, uint32_t* flag, SampleArgs& a)
+{
+  if (const int rc = check_dirs(out_x, out_y, out_z, "out")) return rc;
+  if (!xi0 || !xi1) return fail(BBM_HIP_ERR_INVALID_ARG, "xi pointer is NULL");
+  if (!dir_x || !dir_y || !dir_z || !pdf || !flag) return fail(BBM_HIP_ERR_INVALID_ARG, "sample output pointer is NULL");
+  std::memset(&a, 0, sizeof(a));
+  a.n = n;
+  a.ox = out_x; a.oy = out_y; a.oz = out_z; a.xi0 = xi0; a.xi1 = xi1; a.mask = mask;
+  a.dx = dir_x; a.dy = dir_y; a.dz = dir_z; a.pdf = pdf; a.flag = flag;
+  a.component = component & kFlagAll;
+  return BBM_HIP_OK;
+}
+
+// sample_args, and a value or weight group that is all three pointers or none
+int sample_eval_args(const float* out_x, const float* out_y, const float* out_z, const float* xi0, const float* xi1,
+                     const uint8_t* mask, size_t n, uint32_t component,
+                     float* dir_x, float* dir_y, float* dir_z, float* pdf, uint32_t* flag,
+                     float* r, float* g, float* b, float* wr, float* wg, float* wb, SampleEvalArgs& a)
+{
+  if (const int rc = sample_args(out_x, out_y, out_z, xi0, xi1, mask, n, component, dir_x, dir_y, dir_z, pdf, flag, a.s))
+    return rc;
+  if ((r || g || b) && (!r || !g || !b)) return fail(BBM_HIP_ERR_INVALID_ARG, "value output: give r, g and b or none");
+  if ((wr || wg || wb) && (!wr || !wg || !wb))
+    return fail(BBM_HIP_ERR_INVALID_ARG, "weight output: give wr, wg and wb or none");
+  a.r = r; a.g = g; a.b = b; a.wr = wr; a.wg = wg; a.wb = wb;
+  return BBM_HIP_OK;
+}
+
+int refl_args(const float* out_x, const float* out_y, const float* out_z, const uint8_t* mask, size_t n,
+              uint32_t component, float* r, float* g, float* b, ReflArgs& a)
+{
+  if (const int rc = check_dirs(out_x, out_y, out_z, "out")) return rc;
+  if (!r || !g || !b) return fail(BBM_HIP_ERR_INVALID_ARG, "reflectance output pointer is NULL");
+  std::memset(&a, 0, sizeof(a));
+  a.n = n;
+  a.ox = out_x; a.oy = out_y; a.oz = out_z; a.mask = mask; a.r = r; a.g = g; a.b = b;
+  a.component = component & kFlagAll;
+  return BBM_HIP_OK;
+}
+
+}  // namespace
+
 extern "C" {
 
 int bbm_hip_abi_version(void) { return BBM_HIP_ABI_VERSION; }
@@ -241,17 +318,13 @@ static int eval_common(int mode, int model_id, const float* params, int nparams,
 {
   (void)unit;   // no model on this path depends on unit_t (bsdfmodel/microfacet.h:74, lambertian.h:45)
   const CallExactScope mode_scope(model_id);
-  EvalArgs a;
+  EvalArgs tmp, a;
   const ModelEntry* e;
-  int rc = prepare(model_id, params, nparams, n, a, e);
+  int rc = prepare(model_id, params, nparams, n, tmp, e);
   if (rc) return rc;
   if (n == 0) return BBM_HIP_OK;
-  if ((rc = check_dirs(in_x, in_y, in_z, "in")) || (rc = check_dirs(out_x, out_y, out_z, "out"))) return rc;
-  if ((mode & kModeEval) && (!r || !g || !b)) return fail(BBM_HIP_ERR_INVALID_ARG, "eval output pointer is NULL");
-  if ((mode & kModePdf) && !pdf) return fail(BBM_HIP_ERR_INVALID_ARG, "pdf output pointer is NULL");
-  a.ix = in_x; a.iy = in_y; a.iz = in_z; a.ox = out_x; a.oy = out_y; a.oz = out_z;
-  a.mask = mask; a.r = r; a.g = g; a.b = b; a.pdf = pdf;
-  a.component = component & kFlagAll;
+  if ((rc = eval_args(mode, in_x, in_y, in_z, out_x, out_y, out_z, mask, n, component, r, g, b, pdf, a))) return rc;
+  a.p = tmp.p;
   return e->run.eval_pdf(a, mode, static_cast<hipStream_t>(stream));
 }
 
@@ -299,48 +372,12 @@ int bbm_hip_sample(int model_id, const float* params, int nparams,
   int rc = prepare(model_id, params, nparams, n, tmp, e);
   if (rc) return rc;
   if (n == 0) return BBM_HIP_OK;
-  if ((rc = check_dirs(out_x, out_y, out_z, "out"))) return rc;
-  if (!xi0 || !xi1) return fail(BBM_HIP_ERR_INVALID_ARG, "xi pointer is NULL");
-  if (!dir_x || !dir_y || !dir_z || !pdf || !flag) return fail(BBM_HIP_ERR_INVALID_ARG, "sample output pointer is NULL");
   SampleArgs a;
-  std::memset(&a, 0, sizeof(a));
+  if ((rc = sample_args(out_x, out_y, out_z, xi0, xi1, mask, n, component, dir_x, dir_y, dir_z, pdf, flag, a)))
+    return rc;
   a.p = tmp.p;
-  a.n = n;
-  a.ox = out_x; a.oy = out_y; a.oz = out_z; a.xi0 = xi0; a.xi1 = xi1; a.mask = mask;
-  a.dx = dir_x; a.dy = dir_y; a.dz = dir_z; a.pdf = pdf; a.flag = flag;
-  a.component = component & kFlagAll;
   return e->run.sample(a, static_cast<hipStream_t>(stream));
 }
-
-}  // extern "C"
-
-namespace {
-
-// The checks the two sample_eval calls share once the model (or table) is known, and the argument block: the
-// inputs and dir / pdf / flag are required, a value or weight group is all three pointers or none.
-int sample_eval_args(const float* out_x, const float* out_y, const float* out_z, const float* xi0, const float* xi1,
-                     const uint8_t* mask, size_t n, uint32_t component,
-                     float* dir_x, float* dir_y, float* dir_z, float* pdf, uint32_t* flag,
-                     float* r, float* g, float* b, float* wr, float* wg, float* wb, SampleEvalArgs& a)
-{
-  if (const int rc = check_dirs(out_x, out_y, out_z, "out")) return rc;
-  if (!xi0 || !xi1) return fail(BBM_HIP_ERR_INVALID_ARG, "xi pointer is NULL");
-  if (!dir_x || !dir_y || !dir_z || !pdf || !flag) return fail(BBM_HIP_ERR_INVALID_ARG, "sample output pointer is NULL");
-  if ((r || g || b) && (!r || !g || !b)) return fail(BBM_HIP_ERR_INVALID_ARG, "value output: give r, g and b or none");
-  if ((wr || wg || wb) && (!wr || !wg || !wb))
-    return fail(BBM_HIP_ERR_INVALID_ARG, "weight output: give wr, wg and wb or none");
-  std::memset(&a, 0, sizeof(a));
-  a.s.n = n;
-  a.s.ox = out_x; a.s.oy = out_y; a.s.oz = out_z; a.s.xi0 = xi0; a.s.xi1 = xi1; a.s.mask = mask;
-  a.s.dx = dir_x; a.s.dy = dir_y; a.s.dz = dir_z; a.s.pdf = pdf; a.s.flag = flag;
-  a.r = r; a.g = g; a.b = b; a.wr = wr; a.wg = wg; a.wb = wb;
-  a.s.component = component & kFlagAll;
-  return BBM_HIP_OK;
-}
-
-}  // namespace
-
-extern "C" {
 
 int bbm_hip_sample_eval(int model_id, const float* params, int nparams,
                         const float* out_x, const float* out_y, const float* out_z,
@@ -376,14 +413,9 @@ int bbm_hip_reflectance(int model_id, const float* params, int nparams,
   int rc = prepare(model_id, params, nparams, n, tmp, e);
   if (rc) return rc;
   if (n == 0) return BBM_HIP_OK;
-  if ((rc = check_dirs(out_x, out_y, out_z, "out"))) return rc;
-  if (!r || !g || !b) return fail(BBM_HIP_ERR_INVALID_ARG, "reflectance output pointer is NULL");
   ReflArgs a;
-  std::memset(&a, 0, sizeof(a));
+  if ((rc = refl_args(out_x, out_y, out_z, mask, n, component, r, g, b, a))) return rc;
   a.p = tmp.p;
-  a.n = n;
-  a.ox = out_x; a.oy = out_y; a.oz = out_z; a.mask = mask; a.r = r; a.g = g; a.b = b;
-  a.component = component & kFlagAll;
   return e->run.reflectance(a, static_cast<hipStream_t>(stream));
 }
 
@@ -411,19 +443,15 @@ int bbm_hip_eval_pdf_varying(int model_id, const float* params, int nparams, con
 {
   (void)unit;
   const CallExactScope mode_scope(model_id);
+  EvalArgs tmp;
   EvalVarArgs a;
   const ModelEntry* e;
-  int rc = prepare_var(model_id, params, nparams, varying, n, a.e, a.v, e);
+  int rc = prepare_var(model_id, params, nparams, varying, n, tmp, a.src, e);
   if (rc) return rc;
   if (n == 0) return BBM_HIP_OK;
-  if ((rc = check_dirs(in_x, in_y, in_z, "in")) || (rc = check_dirs(out_x, out_y, out_z, "out"))) return rc;
-  const bool want_eval = r || g || b;
-  if (want_eval && (!r || !g || !b)) return fail(BBM_HIP_ERR_INVALID_ARG, "eval output pointer is NULL");
-  if (!want_eval && !pdf) return fail(BBM_HIP_ERR_INVALID_ARG, "every output pointer is NULL");
-  const int mode = (want_eval ? kModeEval : 0) | (pdf ? kModePdf : 0);
-  a.e.ix = in_x; a.e.iy = in_y; a.e.iz = in_z; a.e.ox = out_x; a.e.oy = out_y; a.e.oz = out_z;
-  a.e.mask = mask; a.e.r = r; a.e.g = g; a.e.b = b; a.e.pdf = pdf;
-  a.e.component = component & kFlagAll;
+  int mode = 0;
+  if ((rc = eval_args(mode, in_x, in_y, in_z, out_x, out_y, out_z, mask, n, component, r, g, b, pdf, a.e))) return rc;
+  a.e.p = tmp.p;
   return e->run.eval_pdf_var(a, mode, static_cast<hipStream_t>(stream));
 }
 
@@ -438,18 +466,12 @@ int bbm_hip_sample_varying(int model_id, const float* params, int nparams, const
   EvalArgs tmp;
   SampleVarArgs a;
   const ModelEntry* e;
-  int rc = prepare_var(model_id, params, nparams, varying, n, tmp, a.v, e);
+  int rc = prepare_var(model_id, params, nparams, varying, n, tmp, a.src, e);
   if (rc) return rc;
   if (n == 0) return BBM_HIP_OK;
-  if ((rc = check_dirs(out_x, out_y, out_z, "out"))) return rc;
-  if (!xi0 || !xi1) return fail(BBM_HIP_ERR_INVALID_ARG, "xi pointer is NULL");
-  if (!dir_x || !dir_y || !dir_z || !pdf || !flag) return fail(BBM_HIP_ERR_INVALID_ARG, "sample output pointer is NULL");
-  std::memset(&a.e, 0, sizeof(a.e));
+  if ((rc = sample_args(out_x, out_y, out_z, xi0, xi1, mask, n, component, dir_x, dir_y, dir_z, pdf, flag, a.e)))
+    return rc;
   a.e.p = tmp.p;
-  a.e.n = n;
-  a.e.ox = out_x; a.e.oy = out_y; a.e.oz = out_z; a.e.xi0 = xi0; a.e.xi1 = xi1; a.e.mask = mask;
-  a.e.dx = dir_x; a.e.dy = dir_y; a.e.dz = dir_z; a.e.pdf = pdf; a.e.flag = flag;
-  a.e.component = component & kFlagAll;
   return e->run.sample_var(a, static_cast<hipStream_t>(stream));
 }
 
@@ -463,16 +485,11 @@ int bbm_hip_reflectance_varying(int model_id, const float* params, int nparams, 
   EvalArgs tmp;
   ReflVarArgs a;
   const ModelEntry* e;
-  int rc = prepare_var(model_id, params, nparams, varying, n, tmp, a.v, e);
+  int rc = prepare_var(model_id, params, nparams, varying, n, tmp, a.src, e);
   if (rc) return rc;
   if (n == 0) return BBM_HIP_OK;
-  if ((rc = check_dirs(out_x, out_y, out_z, "out"))) return rc;
-  if (!r || !g || !b) return fail(BBM_HIP_ERR_INVALID_ARG, "reflectance output pointer is NULL");
-  std::memset(&a.e, 0, sizeof(a.e));
+  if ((rc = refl_args(out_x, out_y, out_z, mask, n, component, r, g, b, a.e))) return rc;
   a.e.p = tmp.p;
-  a.e.n = n;
-  a.e.ox = out_x; a.e.oy = out_y; a.e.oz = out_z; a.e.mask = mask; a.e.r = r; a.e.g = g; a.e.b = b;
-  a.e.component = component & kFlagAll;
   return e->run.reflectance_var(a, static_cast<hipStream_t>(stream));
 }
 
@@ -603,22 +620,12 @@ int bbm_hip_eval_pdf_table(const bbm_hip_table* t, int call_flags, const uint32_
   if (rc) return rc;
   if (n == 0) return BBM_HIP_OK;
   const CallExactScope mode_scope(call_flags);
-  if ((rc = check_dirs(in_x, in_y, in_z, "in")) || (rc = check_dirs(out_x, out_y, out_z, "out"))) return rc;
-  const bool want_eval = r || g || b;
-  if (want_eval && (!r || !g || !b)) return fail(BBM_HIP_ERR_INVALID_ARG, "eval output pointer is NULL");
-  if (!want_eval && !pdf) return fail(BBM_HIP_ERR_INVALID_ARG, "every output pointer is NULL");
-  const int mode = (want_eval ? kModeEval : 0) | (pdf ? kModePdf : 0);
   EvalTabArgs a;
-  std::memset(&a, 0, sizeof(a));
+  int mode = 0;
+  if ((rc = eval_args(mode, in_x, in_y, in_z, out_x, out_y, out_z, mask, n, component, r, g, b, pdf, a.e))) return rc;
   // host_params runs for the uniform call only where a pdf is asked for (launch_mode)
   a.e.p = (mode & kModePdf) ? t->first_prepared : t->first_raw;
-  a.t.blocks = (mode & kModePdf) ? t->prepared : t->raw;
-  a.t.material = material;
-  a.t.count = t->count;
-  a.e.n = n;
-  a.e.ix = in_x; a.e.iy = in_y; a.e.iz = in_z; a.e.ox = out_x; a.e.oy = out_y; a.e.oz = out_z;
-  a.e.mask = mask; a.e.r = r; a.e.g = g; a.e.b = b; a.e.pdf = pdf;
-  a.e.component = component & kFlagAll;
+  a.src = {(mode & kModePdf) ? t->prepared : t->raw, material, t->count};
   return t->e->run.eval_pdf_tab(a, mode, static_cast<hipStream_t>(stream));
 }
 
@@ -633,19 +640,11 @@ int bbm_hip_sample_table(const bbm_hip_table* t, int call_flags, const uint32_t*
   if (rc) return rc;
   if (n == 0) return BBM_HIP_OK;
   const CallExactScope mode_scope(call_flags);
-  if ((rc = check_dirs(out_x, out_y, out_z, "out"))) return rc;
-  if (!xi0 || !xi1) return fail(BBM_HIP_ERR_INVALID_ARG, "xi pointer is NULL");
-  if (!dir_x || !dir_y || !dir_z || !pdf || !flag) return fail(BBM_HIP_ERR_INVALID_ARG, "sample output pointer is NULL");
   SampleTabArgs a;
-  std::memset(&a, 0, sizeof(a));
+  if ((rc = sample_args(out_x, out_y, out_z, xi0, xi1, mask, n, component, dir_x, dir_y, dir_z, pdf, flag, a.e)))
+    return rc;
   a.e.p = t->first_prepared;
-  a.t.blocks = t->prepared;
-  a.t.material = material;
-  a.t.count = t->count;
-  a.e.n = n;
-  a.e.ox = out_x; a.e.oy = out_y; a.e.oz = out_z; a.e.xi0 = xi0; a.e.xi1 = xi1; a.e.mask = mask;
-  a.e.dx = dir_x; a.e.dy = dir_y; a.e.dz = dir_z; a.e.pdf = pdf; a.e.flag = flag;
-  a.e.component = component & kFlagAll;
+  a.src = {t->prepared, material, t->count};
   return t->e->run.sample_tab(a, static_cast<hipStream_t>(stream));
 }
 
@@ -664,15 +663,12 @@ int bbm_hip_sample_eval_table(const bbm_hip_table* t, int call_flags, const uint
   if (n == 0) return BBM_HIP_OK;
   const CallExactScope mode_scope(call_flags);
   SampleEvalTabArgs a;
-  std::memset(&a, 0, sizeof(a));
   if ((rc = sample_eval_args(out_x, out_y, out_z, xi0, xi1, mask, n, component, dir_x, dir_y, dir_z, pdf, flag,
                              r, g, b, wr, wg, wb, a.e)))
     return rc;
   // the block form sample and eval + pdf read (host_params applied)
   a.e.s.p = t->first_prepared;
-  a.t.blocks = t->prepared;
-  a.t.material = material;
-  a.t.count = t->count;
+  a.src = {t->prepared, material, t->count};
   return t->e->run.sample_eval_tab(a, static_cast<hipStream_t>(stream));
 }
 
@@ -686,17 +682,10 @@ int bbm_hip_reflectance_table(const bbm_hip_table* t, int call_flags, const uint
   if (rc) return rc;
   if (n == 0) return BBM_HIP_OK;
   const CallExactScope mode_scope(call_flags);
-  if ((rc = check_dirs(out_x, out_y, out_z, "out"))) return rc;
-  if (!r || !g || !b) return fail(BBM_HIP_ERR_INVALID_ARG, "reflectance output pointer is NULL");
   ReflTabArgs a;
-  std::memset(&a, 0, sizeof(a));
+  if ((rc = refl_args(out_x, out_y, out_z, mask, n, component, r, g, b, a.e))) return rc;
   a.e.p = t->first_raw;
-  a.t.blocks = t->raw;
-  a.t.material = material;
-  a.t.count = t->count;
-  a.e.n = n;
-  a.e.ox = out_x; a.e.oy = out_y; a.e.oz = out_z; a.e.mask = mask; a.e.r = r; a.e.g = g; a.e.b = b;
-  a.e.component = component & kFlagAll;
+  a.src = {t->raw, material, t->count};
   return t->e->run.reflectance_tab(a, static_cast<hipStream_t>(stream));
 }
 

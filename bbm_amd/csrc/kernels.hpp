@@ -249,123 +249,6 @@ void k_eval_pdf_v4(EvalArgs a)
   }
 }
 
-// Eight pairs per thread: two quads, each a fully coalesced 1 KiB wave access (quad t and quad
-// t + 64 within the wave's 128-quad tile).  More independent work per wave for the scheduler.
-template<class Model, int MODE, bool MASK, bool NT>
-__global__ __launch_bounds__(kBlock) BBM_HIP_KERNEL_ATTR void k_eval_pdf_v8(EvalArgs a)
-{
-  math_tables_init();
-  const Model m(a.p.v);
-  const uint64_t n4 = a.n >> 2;
-  const uint64_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const uint64_t stride = uint64_t(gridDim.x) * (2 * kBlock);
-  for (uint64_t base = uint64_t(blockIdx.x) * (2 * kBlock) + wave * 128; base < n4; base += stride)
-  {
-    uint64_t tq[2] = {base + lane, base + 64 + lane};
-    float4 c[2][6];
-    uint32_t cm[2] = {0x01010101u, 0x01010101u};
-#pragma unroll
-    for (int u = 0; u < 2; ++u)
-    {
-      const uint64_t t = tq[u] < n4 ? tq[u] : n4 - 1;
-      c[u][0] = ld4<NT>(a.ix, t); c[u][1] = ld4<NT>(a.iy, t); c[u][2] = ld4<NT>(a.iz, t);
-      c[u][3] = ld4<NT>(a.ox, t); c[u][4] = ld4<NT>(a.oy, t); c[u][5] = ld4<NT>(a.oz, t);
-      if (MASK) cm[u] = reinterpret_cast<const uint32_t*>(a.mask)[t];
-    }
-    float r[2][4], g[2][4], b[2][4], p[2][4];
-#pragma unroll
-    for (int u = 0; u < 2; ++u)
-    {
-      const float inx[4] = {c[u][0].x, c[u][0].y, c[u][0].z, c[u][0].w}, iny[4] = {c[u][1].x, c[u][1].y, c[u][1].z, c[u][1].w};
-      const float inz[4] = {c[u][2].x, c[u][2].y, c[u][2].z, c[u][2].w}, onx[4] = {c[u][3].x, c[u][3].y, c[u][3].z, c[u][3].w};
-      const float ony[4] = {c[u][4].x, c[u][4].y, c[u][4].z, c[u][4].w}, onz[4] = {c[u][5].x, c[u][5].y, c[u][5].z, c[u][5].w};
-#pragma unroll
-      for (int j = 0; j < 4; ++j)
-      {
-        float rgb[3];
-        const uint32_t comp = ((cm[u] >> (8 * j)) & 0xffu) ? a.component : 0u;
-        m.template eval_pdf<MODE>(mk3(inx[j], iny[j], inz[j]), mk3(onx[j], ony[j], onz[j]), comp, rgb, p[u][j]);
-        r[u][j] = rgb[0]; g[u][j] = rgb[1]; b[u][j] = rgb[2];
-      }
-    }
-#pragma unroll
-    for (int u = 0; u < 2; ++u)
-    {
-      if (tq[u] >= n4) continue;
-      const uint64_t t = tq[u];
-      if (MODE & kModeEval)
-      {
-        st4<NT>(a.r, t, r[u][0], r[u][1], r[u][2], r[u][3]);
-        st4<NT>(a.g, t, g[u][0], g[u][1], g[u][2], g[u][3]);
-        st4<NT>(a.b, t, b[u][0], b[u][1], b[u][2], b[u][3]);
-      }
-      if (MODE & kModePdf) st4<NT>(a.pdf, t, p[u][0], p[u][1], p[u][2], p[u][3]);
-    }
-  }
-  if (blockIdx.x == 0 && threadIdx.x < (a.n & 3))
-  {
-    const uint64_t i = (n4 << 2) + threadIdx.x;
-    one_pair<Model, MODE>(m, a, i, MASK ? (a.mask[i] != 0) : true);
-  }
-}
-
-// Software-pipelined grid-stride variant: the six 16-byte loads of the thread's NEXT quad are
-// issued before the current quad is computed, so every wave keeps HBM reads in flight while its
-// VALU work runs (the plain kernel only overlaps load and compute across different waves).
-template<class Model, int MODE, bool MASK, bool NT>
-__global__ __launch_bounds__(kBlock) void k_eval_pdf_pipe(EvalArgs a)
-{
-  math_tables_init();
-  const Model m(a.p.v);
-  const uint64_t n4 = a.n >> 2;
-  const uint64_t stride = uint64_t(gridDim.x) * kBlock;
-  uint64_t t = uint64_t(blockIdx.x) * kBlock + threadIdx.x;
-  if (t < n4)
-  {
-    float4 c[6];
-    uint32_t cm = 0x01010101u;
-    c[0] = ld4<NT>(a.ix, t); c[1] = ld4<NT>(a.iy, t); c[2] = ld4<NT>(a.iz, t);
-    c[3] = ld4<NT>(a.ox, t); c[4] = ld4<NT>(a.oy, t); c[5] = ld4<NT>(a.oz, t);
-    if (MASK) cm = reinterpret_cast<const uint32_t*>(a.mask)[t];
-    for (; t < n4; t += stride)
-    {
-      const uint64_t tn = (t + stride < n4) ? t + stride : t;   // clamped: the last prefetch re-reads
-      float4 nx[6];
-      uint32_t nm = 0x01010101u;
-      nx[0] = ld4<NT>(a.ix, tn); nx[1] = ld4<NT>(a.iy, tn); nx[2] = ld4<NT>(a.iz, tn);
-      nx[3] = ld4<NT>(a.ox, tn); nx[4] = ld4<NT>(a.oy, tn); nx[5] = ld4<NT>(a.oz, tn);
-      if (MASK) nm = reinterpret_cast<const uint32_t*>(a.mask)[tn];
-      const float inx[4] = {c[0].x, c[0].y, c[0].z, c[0].w}, iny[4] = {c[1].x, c[1].y, c[1].z, c[1].w};
-      const float inz[4] = {c[2].x, c[2].y, c[2].z, c[2].w}, onx[4] = {c[3].x, c[3].y, c[3].z, c[3].w};
-      const float ony[4] = {c[4].x, c[4].y, c[4].z, c[4].w}, onz[4] = {c[5].x, c[5].y, c[5].z, c[5].w};
-      float r[4], g[4], b[4], p[4];
-#pragma unroll
-      for (int j = 0; j < 4; ++j)
-      {
-        float rgb[3];
-        const uint32_t comp = ((cm >> (8 * j)) & 0xffu) ? a.component : 0u;
-        m.template eval_pdf<MODE>(mk3(inx[j], iny[j], inz[j]), mk3(onx[j], ony[j], onz[j]), comp, rgb, p[j]);
-        r[j] = rgb[0]; g[j] = rgb[1]; b[j] = rgb[2];
-      }
-      if (MODE & kModeEval)
-      {
-        st4<NT>(a.r, t, r[0], r[1], r[2], r[3]);
-        st4<NT>(a.g, t, g[0], g[1], g[2], g[3]);
-        st4<NT>(a.b, t, b[0], b[1], b[2], b[3]);
-      }
-      if (MODE & kModePdf) st4<NT>(a.pdf, t, p[0], p[1], p[2], p[3]);
-#pragma unroll
-      for (int k = 0; k < 6; ++k) c[k] = nx[k];
-      cm = nm;
-    }
-  }
-  if (blockIdx.x == 0 && threadIdx.x < (a.n & 3))
-  {
-    const uint64_t i = (n4 << 2) + threadIdx.x;
-    one_pair<Model, MODE>(m, a, i, MASK ? (a.mask[i] != 0) : true);
-  }
-}
-
 // Scalar path for unaligned arrays.
 template<class Model, int MODE, bool MASK, bool EXACT = false>
 __global__ __launch_bounds__(kBlock) void k_eval_pdf_v1(EvalArgs a)
@@ -690,9 +573,8 @@ __global__ __launch_bounds__(kBlock) BBM_HIP_COMPACT_ATTR void k_eval_pdf_compac
   }
 }
 
-// Grid cap for the grid-stride kernels.  Launch-variant knobs (BBM_HIP_MAX_BLOCKS, BBM_HIP_PPT = 8 pairs per thread,
-// BBM_HIP_PIPE = the software-pipelined kernel, BBM_HIP_NT = 0 temporal loads / stores) exist only in an
-// experimental build (-DBBM_HIP_EXPERIMENTAL, tools/build_variant.sh): the shipped library reads no tuning knob.
+// Grid cap for the grid-stride kernels.  Launch-variant knobs (BBM_HIP_MAX_BLOCKS, BBM_HIP_NT = 0 temporal loads /
+// stores) exist only in an experimental build (-DBBM_HIP_EXPERIMENTAL, tools/build_variant.sh): the shipped library reads no tuning knob.
 #ifdef BBM_HIP_EXPERIMENTAL
 inline uint64_t max_blocks()
 {
@@ -700,24 +582,6 @@ inline uint64_t max_blocks()
     const char* e = std::getenv("BBM_HIP_MAX_BLOCKS");
     const long long x = e ? std::atoll(e) : 0;
     return x > 0 ? uint64_t(x) : uint64_t(kMaxBlocks);
-  }();
-  return v;
-}
-
-inline int pairs_per_thread()
-{
-  static const int v = [] {
-    const char* e = std::getenv("BBM_HIP_PPT");
-    return (e && std::atoi(e) == 8) ? 8 : 4;
-  }();
-  return v;
-}
-
-inline bool use_pipe()
-{
-  static const bool v = [] {
-    const char* e = std::getenv("BBM_HIP_PIPE");
-    return e ? std::atoi(e) != 0 : false;
   }();
   return v;
 }
@@ -824,21 +688,13 @@ int launch_mode(const EvalArgs& a0, hipStream_t s)
   if (MODE & kModeEval) vec = vec && aligned16(a.r) && aligned16(a.g) && aligned16(a.b);
   if (MODE & kModePdf) vec = vec && aligned16(a.pdf);
   const uint64_t units = vec ? (a.n >> 2) : a.n;
-#ifdef BBM_HIP_EXPERIMENTAL
-  // A/B variants (tools/gpu_ab.sh): 8 pairs/thread, software pipelining, temporal loads/stores.
-  const uint64_t per_block = (vec && pairs_per_thread() == 8) ? 2 * kBlock : kBlock;
-#else
-  const uint64_t per_block = kBlock;
-#endif
-  uint64_t blocks = (units + per_block - 1) / per_block;
+  uint64_t blocks = (units + kBlock - 1) / kBlock;
   if (blocks < 1) blocks = 1;
   if (blocks > max_blocks()) blocks = max_blocks();
   if (eval_grid_cap<Model>::value && blocks > eval_grid_cap<Model>::value) blocks = eval_grid_cap<Model>::value;
 #ifdef BBM_HIP_EXPERIMENTAL
-  if (vec && pairs_per_thread() == 8)
-    hipLaunchKernelGGL((k_eval_pdf_v8<Model, MODE, MASK, true>), dim3(unsigned(blocks)), dim3(kBlock), 0, s, a);
-  else if (vec && use_pipe()) hipLaunchKernelGGL((k_eval_pdf_pipe<Model, MODE, MASK, true>), dim3(unsigned(blocks)), dim3(kBlock), 0, s, a);
-  else if (vec && !use_nt()) hipLaunchKernelGGL((k_eval_pdf_v4<Model, MODE, MASK, false>), dim3(unsigned(blocks)), dim3(kBlock), 0, s, a);
+  // A/B variant (tools/gpu_ab.sh): temporal loads / stores
+  if (vec && !use_nt()) hipLaunchKernelGGL((k_eval_pdf_v4<Model, MODE, MASK, false>), dim3(unsigned(blocks)), dim3(kBlock), 0, s, a);
   else
 #endif
   if (vec && compact_eval<Model>::value && use_compact())
@@ -1297,6 +1153,7 @@ int launch_loss(const LossArgs& a0, hipStream_t s)
 #include "image.hpp"
 #include "varying.hpp"
 #include "table.hpp"
+#include "lanes.hpp"
 #include "sample_eval.hpp"
 
 namespace bbmhip {
@@ -1326,11 +1183,11 @@ struct Launchers
   LossLauncher loss;
   CheckLauncher check;
   ImageLauncher image;
-  // per-lane parameters (varying.hpp); all null where the composition has none (supports_varying)
+  // per-lane parameters (lanes.hpp over VarRows); all null where the composition has none (supports_varying)
   EvalVarLauncher eval_pdf_var;
   SampleVarLauncher sample_var;
   ReflVarLauncher reflectance_var;
-  // material tables (table.hpp): a material's block on the host and the three kernels; null for the same rows
+  // material tables (lanes.hpp over TabRef): a material's block on the host and the three kernels; null for the same rows
   TablePrepare table_prepare;
   EvalTabLauncher eval_pdf_tab;
   SampleTabLauncher sample_tab;
@@ -1343,8 +1200,10 @@ template<class M> constexpr Launchers launchers()
 {
   if constexpr (supports_varying<M>::value)
     return {&launch_eval_pdf<M>, &launch_sample<M>, &launch_reflectance<M>, &launch_loss<M>, &launch_check<M>, &launch_image<M>,
-            &launch_eval_pdf_var<M>, &launch_sample_var<M>, &launch_reflectance_var<M>,
-            &table_prepare<M>, &launch_eval_pdf_tab<M>, &launch_sample_tab<M>, &launch_reflectance_tab<M>,
+            &launch_eval_pdf_lanes<M, EvalVarArgs>, &launch_sample_lanes<M, SampleVarArgs>,
+            &launch_reflectance_lanes<M, ReflVarArgs>,
+            &table_prepare<M>, &launch_eval_pdf_lanes<M, EvalTabArgs>, &launch_sample_lanes<M, SampleTabArgs>,
+            &launch_reflectance_lanes<M, ReflTabArgs>,
             &launch_sample_eval<M>, &launch_sample_eval_tab<M>};
   else
     return {&launch_eval_pdf<M>, &launch_sample<M>, &launch_reflectance<M>, &launch_loss<M>, &launch_check<M>, &launch_image<M>,

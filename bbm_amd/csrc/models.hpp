@@ -220,13 +220,13 @@ template<> struct sample_eval_tab_quad<AggNganCookTorranceM, true> { static cons
   template int launch_loss<M>(const LossArgs&, hipStream_t);                  \
   template int launch_check<M>(int, const CheckArgs&, double*, hipStream_t);    \
   template int launch_image<M>(const ImageArgs&, hipStream_t);                \
-  template int launch_eval_pdf_var<M>(const EvalVarArgs&, int, hipStream_t);  \
-  template int launch_sample_var<M>(const SampleVarArgs&, hipStream_t);       \
-  template int launch_reflectance_var<M>(const ReflVarArgs&, hipStream_t);    \
+  template int launch_eval_pdf_lanes<M, EvalVarArgs>(const EvalVarArgs&, int, hipStream_t);  \
+  template int launch_sample_lanes<M, SampleVarArgs>(const SampleVarArgs&, hipStream_t);       \
+  template int launch_reflectance_lanes<M, ReflVarArgs>(const ReflVarArgs&, hipStream_t);    \
   template int table_prepare<M>(const ParamBlock&, bool, hipStream_t, TableBlocks&); \
-  template int launch_eval_pdf_tab<M>(const EvalTabArgs&, int, hipStream_t);  \
-  template int launch_sample_tab<M>(const SampleTabArgs&, hipStream_t);       \
-  template int launch_reflectance_tab<M>(const ReflTabArgs&, hipStream_t);    \
+  template int launch_eval_pdf_lanes<M, EvalTabArgs>(const EvalTabArgs&, int, hipStream_t);  \
+  template int launch_sample_lanes<M, SampleTabArgs>(const SampleTabArgs&, hipStream_t);       \
+  template int launch_reflectance_lanes<M, ReflTabArgs>(const ReflTabArgs&, hipStream_t);    \
   template int launch_sample_eval<M>(const SampleEvalArgs&, hipStream_t);     \
   template int launch_sample_eval_tab<M>(const SampleEvalTabArgs&, hipStream_t);
 #define BBM_HIP_EXTERN(M)                                                       \
@@ -236,12 +236,12 @@ template<> struct sample_eval_tab_quad<AggNganCookTorranceM, true> { static cons
   extern template int launch_loss<M>(const LossArgs&, hipStream_t);           \
   extern template int launch_check<M>(int, const CheckArgs&, double*, hipStream_t); \
   extern template int launch_image<M>(const ImageArgs&, hipStream_t);         \
-  extern template int launch_eval_pdf_var<M>(const EvalVarArgs&, int, hipStream_t); \
-  extern template int launch_sample_var<M>(const SampleVarArgs&, hipStream_t); \
-  extern template int launch_reflectance_var<M>(const ReflVarArgs&, hipStream_t); \
+  extern template int launch_eval_pdf_lanes<M, EvalVarArgs>(const EvalVarArgs&, int, hipStream_t); \
+  extern template int launch_sample_lanes<M, SampleVarArgs>(const SampleVarArgs&, hipStream_t); \
+  extern template int launch_reflectance_lanes<M, ReflVarArgs>(const ReflVarArgs&, hipStream_t); \
   extern template int table_prepare<M>(const ParamBlock&, bool, hipStream_t, TableBlocks&); \
-  extern template int launch_eval_pdf_tab<M>(const EvalTabArgs&, int, hipStream_t); \
-  extern template int launch_sample_tab<M>(const SampleTabArgs&, hipStream_t); \
-  extern template int launch_reflectance_tab<M>(const ReflTabArgs&, hipStream_t); \
+  extern template int launch_eval_pdf_lanes<M, EvalTabArgs>(const EvalTabArgs&, int, hipStream_t); \
+  extern template int launch_sample_lanes<M, SampleTabArgs>(const SampleTabArgs&, hipStream_t); \
+  extern template int launch_reflectance_lanes<M, ReflTabArgs>(const ReflTabArgs&, hipStream_t); \
   extern template int launch_sample_eval<M>(const SampleEvalArgs&, hipStream_t); \
   extern template int launch_sample_eval_tab<M>(const SampleEvalTabArgs&, hipStream_t);

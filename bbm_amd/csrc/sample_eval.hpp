@@ -1,6 +1,6 @@
 // bbm_amd/csrc/sample_eval.hpp -- one BSDF call per bounce in one launch: draw a direction for `out`, evaluate the
 // model at (dir, out) and form the path's throughput weight eval . cos / pdf (bbm_hip_sample_eval and its material
-// table twin bbm_hip_sample_eval_table).  Included at the end of kernels.hpp, after table.hpp.
+// table twin bbm_hip_sample_eval_table).  Included at the end of kernels.hpp, after lanes.hpp.
 //
 // Lane i returns what the staged pair of calls returns for it, bit for bit: dir / pdf / flag are bbm_hip_sample's,
 // value is the r, g, b of bbm_hip_eval_pdf (both outputs) at in = dir, and weight[c] is
@@ -23,7 +23,7 @@ struct SampleEvalArgs
   float* r; float* g; float* b;       // value = eval(dir, out); all null: not stored
   float* wr; float* wg; float* wb;    // weight; all null: not stored
 };
-struct SampleEvalTabArgs { SampleEvalArgs e; TabRef t; };     // e.s.p: the fallback block (table.hpp)
+struct SampleEvalTabArgs : LaneArgs<SampleEvalArgs, TabRef> {};     // e.s.p: the fallback block (table.hpp)
 
 template<class Model> constexpr bool fused_sample_eval()
 {
@@ -174,23 +174,26 @@ __global__ __launch_bounds__(kBlock) BBM_HIP_SAMPLE_EVAL_ATTR(Model) void k_samp
     one_sample_eval<EXACT>(m, a, i, a.s.mask ? (a.s.mask[i] != 0) : true);
 }
 
-// Material tables: the same lane behind table.hpp's block gather and index load.  S: the slot count of the model the
-// table was made for (Model may be its exact-mode sampling twin).  One model is live at a time.
-template<class Model, int S, bool EXACT>
-__device__ __forceinline__ void tab_one_sample_eval(const SampleEvalTabArgs& a, uint64_t i)
+// Material tables: the same lane behind a lane-parameter source (lanes.hpp; instantiated for TabRef only, there is
+// no per-row entry point).  S: the slot count of the model the table was made for (Model may be its exact-mode
+// sampling twin).  One model is live at a time.
+template<class Model, int S, bool EXACT, class A>
+__device__ __forceinline__ void lane_one_sample_eval(const A& a, uint64_t i)
 {
   const SampleArgs& s = a.e.s;
-  const uint32_t id = a.t.material[i];
+  const auto l = a.src.load_lane(i);
   ParamBlock q;
-  tab_block<S>(s.p, a.t, id, q);
+  a.src.template lane_block<S>(s.p, l, i, q);
   const Model m(q.v);
-  one_sample_eval<EXACT>(m, a.e, i, (s.mask ? (s.mask[i] != 0) : true) && id < a.t.count);
+  bool active = s.mask ? (s.mask[i] != 0) : true;
+  active = active && a.src.lane_live(l);
+  one_sample_eval<EXACT>(m, a.e, i, active);
 }
 
-// Four lanes per thread; every float array and the index array 16-byte aligned, the mask 4-byte aligned.  A full
-// grid, as the other table kernels.
-template<class Model, int S, bool EXACT>
-__global__ __launch_bounds__(kBlock) BBM_HIP_SAMPLE_EVAL_ATTR(Model) void k_sample_eval_tab(SampleEvalTabArgs a)
+// Four lanes per thread; every float array and the source's own 16-byte aligned, the mask 4-byte aligned.  A full
+// grid, as the other per-lane kernels.
+template<class Model, int S, bool EXACT, class A>
+__global__ __launch_bounds__(kBlock) BBM_HIP_SAMPLE_EVAL_ATTR(Model) void k_seval_lane4(A a)
 {
   math_tables_init();
   const SampleArgs& s = a.e.s;
@@ -200,10 +203,8 @@ __global__ __launch_bounds__(kBlock) BBM_HIP_SAMPLE_EVAL_ATTR(Model) void k_samp
   {
     const float4 ox = ld4<true>(s.ox, t), oy = ld4<true>(s.oy, t), oz = ld4<true>(s.oz, t);
     const float4 x0 = ld4<true>(s.xi0, t), x1 = ld4<true>(s.xi1, t);
-    typedef uint32_t u4 __attribute__((ext_vector_type(4)));
-    const u4 idv = __builtin_nontemporal_load(reinterpret_cast<const u4*>(a.t.material) + t);
+    const auto c = a.src.template load_quad<S>(t);
     const uint32_t mk = s.mask ? reinterpret_cast<const uint32_t*>(s.mask)[t] : 0x01010101u;
-    const uint32_t id[4] = {idv.x, idv.y, idv.z, idv.w};
     const float onx[4] = {ox.x, ox.y, ox.z, ox.w}, ony[4] = {oy.x, oy.y, oy.z, oy.w}, onz[4] = {oz.x, oz.y, oz.z, oz.w};
     const float u0[4] = {x0.x, x0.y, x0.z, x0.w}, u1[4] = {x1.x, x1.y, x1.z, x1.w};
     float dx[4], dy[4], dz[4], pd[4], rgb[3][4];
@@ -212,29 +213,31 @@ __global__ __launch_bounds__(kBlock) BBM_HIP_SAMPLE_EVAL_ATTR(Model) void k_samp
     for (int j = 0; j < 4; ++j)
     {
       ParamBlock q;
-      tab_block<S>(s.p, a.t, id[j], q);
+      a.src.template quad_block<S>(s.p, c, j, q);
       const Model m(q.v);
       v3 d;
       float f[3];
-      const uint32_t comp = (((mk >> (8 * j)) & 0xffu) && id[j] < a.t.count) ? s.component : 0u;
+      bool active = (mk >> (8 * j)) & 0xffu;
+      active = active && a.src.quad_live(c, j);
+      const uint32_t comp = active ? s.component : 0u;
       model_sample_eval<EXACT>(m, mk3(onx[j], ony[j], onz[j]), u0[j], u1[j], comp, d, f, pd[j], fl[j]);
       dx[j] = d.x; dy[j] = d.y; dz[j] = d.z;
 #pragma unroll
-      for (int c = 0; c < 3; ++c) rgb[c][j] = f[c];
+      for (int c3 = 0; c3 < 3; ++c3) rgb[c3][j] = f[c3];
     }
     store_sample_eval(a.e, t, dx, dy, dz, pd, fl, rgb);
   }
   // tail
-  if (blockIdx.x == 0 && threadIdx.x < (s.n & 3)) tab_one_sample_eval<Model, S, EXACT>(a, (n4 << 2) + threadIdx.x);
+  if (blockIdx.x == 0 && threadIdx.x < (s.n & 3)) lane_one_sample_eval<Model, S, EXACT>(a, (n4 << 2) + threadIdx.x);
 }
 
 // One lane per thread: unaligned arrays (and the rows sample_eval_tab_quad excludes).
-template<class Model, int S, bool EXACT>
-__global__ __launch_bounds__(kBlock) BBM_HIP_SAMPLE_EVAL_ATTR(Model) void k_sample_eval_tab1(SampleEvalTabArgs a)
+template<class Model, int S, bool EXACT, class A>
+__global__ __launch_bounds__(kBlock) BBM_HIP_SAMPLE_EVAL_ATTR(Model) void k_seval_lane1(A a)
 {
   math_tables_init();
   const uint64_t i = uint64_t(blockIdx.x) * kBlock + threadIdx.x;
-  if (i < a.e.s.n) tab_one_sample_eval<Model, S, EXACT>(a, i);
+  if (i < a.e.s.n) lane_one_sample_eval<Model, S, EXACT>(a, i);
 }
 
 inline bool sample_eval_aligned(const SampleEvalArgs& a)
@@ -288,23 +291,23 @@ int launch_sample_eval(const SampleEvalArgs& a0, hipStream_t s)
   return BBM_HIP_OK;
 }
 
-// a full grid, as the other table kernels; 0 where the batch is too large for one launch (var_blocks)
+// a full grid, as the other per-lane kernels; 0 where the batch is too large for one launch (var_blocks)
 template<class K, int S, bool E, bool QUAD>
 unsigned launch_sample_eval_tab_kernel(const SampleEvalTabArgs& a, hipStream_t s)
 {
-  const bool vec = QUAD && sample_eval_aligned(a.e) && aligned16(a.t.material);
+  const bool vec = QUAD && sample_eval_aligned(a.e) && a.src.aligned(S);
   const unsigned blocks = var_blocks(vec ? (a.e.s.n >> 2) : a.e.s.n);
   if (blocks == 0) return blocks;
   if constexpr (QUAD)
   {
-    if (vec) hipLaunchKernelGGL((k_sample_eval_tab<K, S, E>), dim3(blocks), dim3(kBlock), 0, s, a);
+    if (vec) hipLaunchKernelGGL((k_seval_lane4<K, S, E, SampleEvalTabArgs>), dim3(blocks), dim3(kBlock), 0, s, a);
   }
-  if (!vec) hipLaunchKernelGGL((k_sample_eval_tab1<K, S, E>), dim3(blocks), dim3(kBlock), 0, s, a);
+  if (!vec) hipLaunchKernelGGL((k_seval_lane1<K, S, E, SampleEvalTabArgs>), dim3(blocks), dim3(kBlock), 0, s, a);
   return blocks;
 }
 
 // The table's blocks were prepared at create (table_prepare: host_prepare, host_validate, host_params per material),
-// so, as launch_sample_tab, nothing is left to do on the host but choose the kernel.
+// so, as for launch_sample_lanes, nothing is left to do on the host but choose the kernel.
 template<class Model>
 int launch_sample_eval_tab(const SampleEvalTabArgs& a, hipStream_t s)
 {

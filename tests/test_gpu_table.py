@@ -1,5 +1,6 @@
-"""Material tables (bbm_amd/csrc/table.hpp: k_eval_pdf_tab, k_eval_pdf_tab1, k_sample_tab, k_reflectance_tab behind
-bbm_hip_table_* / bbm_hip_*_table and bbm_amd.MaterialTable).
+"""Material tables (bbm_amd/csrc/table.hpp, the table source of the per-lane kernels in lanes.hpp: k_eval_lane4,
+k_eval_lane1, k_sample_lane, k_refl_lane behind bbm_hip_table_* / bbm_hip_*_table and
+bbm_amd.MaterialTable).
 
 The contract: lane i's output is what the uniform entry point returns for that pair with material material[i]'s
 parameter vector, bit for bit ("bit for bit" = equal int32 views), EPD included; a lane whose index is out of range
@@ -19,7 +20,8 @@ and `out` over the sphere, xi from the library's generator.
   8. a 5 000-material table (the implementation has no size threshold: one gather path for every M);
   9. the mixed batch against the reference: zero lanes outside the parity bar;
  10. lifetime: two tables, reuse, a side stream, destroy and create again, create on one stream and use on another;
-     and the batch calls' argument errors on a live table.
+     and the batch calls' argument errors on a live table;
+ 11. the table call against the per-lane-rows call over the same parameters: two sources behind shared kernels.
 """
 import ctypes
 import json
@@ -130,6 +132,15 @@ def uniform(name, common):
     if name not in _UNIFORM:
         _UNIFORM[name] = per_material(name, sets_of(name), common.din, common.dout, common.xi)
     return _UNIFORM[name]
+
+
+def off1(x):
+    """x's rows one element into a buffer of odd pitch: 4-byte aligned, not 16."""
+    buf = torch.zeros(x.shape[:-1] + (x.shape[-1] + 1,), dtype=x.dtype, device="cuda")
+    buf[..., 1:] = x
+    v = buf[..., 1:]
+    assert v.data_ptr() % 16 and v.data_ptr() % 4 == 0
+    return v
 
 
 def same(got, want, what):
@@ -249,14 +260,6 @@ def test_unaligned_arrays(bbm, common, name):
     t = bbm.MaterialTable(name, sets)
     assign = common.rng.integers(0, M, N)
     want = select(per, assign)
-
-    def off1(x):
-        """x's rows one element into a buffer of odd pitch: 4-byte aligned, not 16."""
-        buf = torch.zeros(x.shape[:-1] + (x.shape[-1] + 1,), dtype=x.dtype, device="cuda")
-        buf[..., 1:] = x
-        v = buf[..., 1:]
-        assert v.data_ptr() % 16 and v.data_ptr() % 4 == 0
-        return v
     idx = idx_t(assign)
     uin, uout, uxi, uidx = off1(common.din), off1(common.dout), off1(common.xi), off1(idx)
     rows = lambda v: tuple(v[k] for k in range(v.shape[0]))
@@ -384,6 +387,77 @@ def test_against_the_reference(bbm, common, name):
     bad = ou.parity_violations(got, want)
     print(f"{name}: max rel {np.nanmax(ou.rel_err(got, want)):.3e}, {bad[0].size} lanes outside the bar")
     assert bad[0].size == 0, (name, bad, got[bad], want[bad])
+
+
+# ------------------------------------------------------------------------ 11. the table source against the rows source
+
+def five_sets(name):
+    """M = 5 parameter sets of a row: CookTorrance's ramp, else five points on the segment between the row's first two
+    golden sets (the bounds are a box, so every point is a valid set).  EPD: p is material 0's in every set."""
+    if name == "CookTorrance":
+        return ramp(5)
+    s = sets_of(name)
+    t = np.linspace(0.0, 1.0, 5, dtype=F)[:, None]
+    sets = ((F(1) - t) * s[0] + t * s[1]).astype(F)
+    if name == "EPD":
+        sets[:, 1] = sets[0, 1]
+    assert len(np.unique(sets, axis=0)) == 5
+    return sets
+
+
+@pytest.mark.parametrize("name,exact", [("CookTorrance", False), ("CookTorrance", True),
+                                        ("Aggregate<Lambertian,Bagher>", False), ("EPD", False)])
+def test_table_and_rows_sources_agree(bbm, common, name, exact):
+    """The table and the per-lane-rows calls run the same kernels over two parameter sources (lanes.hpp; only the rows'
+    quad eval kernel has a body of its own), so they are held to each other: a table of five sets indexed at random, against the varying call whose rows are those sets
+    gathered by the same indices on the host and whose uniform vector is material 0.  eval_pdf, reflectance and sample
+    agree bit for bit, under a mask, with every array 16-byte aligned (CookTorrance, EPD: the quad kernels; the
+    33-parameter aggregate: the rows' one-pair kernel against the table's quad) and one float into its buffer (the
+    one-lane kernels), and an index of -1 is the varying lane with mask = 0.
+    EPD's sets share one p.  That is a condition of the comparison, not a tolerance: where p varies per lane the rows
+    path takes the device's tgamma for the lanes whose p is not the uniform vector's, the table the host's tgammaf
+    per material, and the two round differently."""
+    sets = five_sets(name)
+    M, P = sets.shape
+    assign = common.rng.integers(0, M, N)
+    out = np.zeros(N, bool)
+    out[3::11] = True                            # every residue mod 4, the first and the last quad, the tail lane
+    out[[0, N - 1]] = True
+    raw = np.where(out, -1, assign)
+    gathered = sets[np.where(out, 0, assign)]    # an index out of range reads the fallback: material 0
+    rows = torch.from_numpy(np.ascontiguousarray(gathered.T)).cuda()
+    idx = torch.from_numpy(raw.astype(np.int32)).cuda()
+    in_range = torch.from_numpy((~out).astype(np.uint8)).cuda()
+    t, m = bbm.MaterialTable(name, sets), model_at(name, sets[0])
+    tup = lambda v: tuple(v[k] for k in range(v.shape[0]))
+
+    def pitch4(x):
+        """x's rows in a buffer whose pitch is a multiple of four floats: every row 16-byte aligned (the rows of a
+        (3, N) tensor are not, N being odd)."""
+        buf = torch.zeros(x.shape[:-1] + ((x.shape[-1] + 3) & ~3,), dtype=x.dtype, device="cuda")
+        buf[..., :x.shape[-1]] = x
+        v = buf[..., :x.shape[-1]]
+        assert all(r.data_ptr() % 16 == 0 for r in (v if v.dim() == 2 else [v]))
+        return v
+
+    def calls(model, din, dout, xi, place, **kw):
+        """run(), with eval_pdf writing into buffers placed like the inputs (the quad kernel needs them aligned)."""
+        rgb = place(torch.zeros((3, N), dtype=torch.float32, device="cuda"))
+        pdf = place(torch.zeros((N,), dtype=torch.float32, device="cuda"))
+        model.eval_pdf(din, dout, rgb=rgb, pdf=pdf, **kw)
+        refl, s = model.reflectance(dout, **kw), model.sample(dout, xi, **kw)
+        return np.concatenate([i32(rgb), i32(pdf)[None], i32(refl), i32(s.direction), i32(s.pdf)[None], i32(s.flag)[None]])
+
+    for what, place in (("aligned", pitch4), ("one float in", off1)):
+        din, dout, xi = tup(place(common.din)), tup(place(common.dout)), tup(place(common.xi))
+        vrows = place(rows)
+        got_t = calls(t, din, dout, xi, place, material=place(idx), mask=common.mask, exact=exact)
+        got_v = calls(m, din, dout, xi, place, varying={k: vrows[k] for k in range(P)}, mask=common.mask & in_range,
+                      exact=exact)
+        open_ = (common.mask.cpu().numpy() != 0) & ~out
+        assert got_t[:4, open_].any() and not got_t[:7, ~open_].any(), (name, what)
+        same(got_t, got_v, (name, exact, what))
+    t.close()
 
 
 # ------------------------------------------------------------------------ 10. lifetime, arguments

@@ -1,5 +1,5 @@
-"""Per-lane model parameters (bbm_amd/csrc/varying.hpp: k_eval_pdf_var, k_eval_pdf_var1, k_sample_var,
-k_reflectance_var behind bbm_hip_*_varying and the `varying=` keyword of BsdfModel).
+"""Per-lane model parameters (bbm_amd/csrc/varying.hpp, the rows source of lanes.hpp's k_eval_pdf_var, k_eval_lane1,
+k_sample_lane and k_refl_lane, behind bbm_hip_*_varying and the `varying=` keyword of BsdfModel).
 
 The contract: lane i's output is what the uniform entry point returns for that pair at lane i's parameter vector, bit
 for bit ("bit for bit" = equal int32 views, so NaN for NaN).  Common inputs: N = 1217 pairs (4 x 256 + 3 x 64 + 1)
