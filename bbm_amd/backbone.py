@@ -151,6 +151,62 @@ def _sample_eval_inputs(out, xi):
     return ox, oy, oz, n, x0, x1
 
 
+def _lanes(t):
+    """The lane count a direction argument seems to have (a (3, N) tensor or three rows), or None: for checks that
+    run before that argument's own."""
+    torch = _torch()
+    t = t[0] if isinstance(t, (tuple, list)) and len(t) > 0 else t
+    return int(t.shape[-1]) if isinstance(t, torch.Tensor) and t.dim() >= 1 else None
+
+
+def _normal_rows(normal, like, what="normal"):
+    """The shading normals of the world-space calls, checked before anything else is: a (3, N) float32 CUDA tensor
+    with contiguous rows, one normal per lane of `like` -> its three row pointers.  Wrong dtype (float64 included) or
+    device: TypeError; wrong shape, length or stride: ValueError."""
+    torch = _torch()
+    if not isinstance(normal, torch.Tensor) or normal.dtype != torch.float32:
+        raise TypeError(f"{what}: floatRGB only, expected a (3, N) float32 CUDA tensor")
+    if normal.dim() != 2 or normal.shape[0] != 3:
+        raise ValueError(f"{what}: expected a (3, N) tensor, got {tuple(normal.shape)}")
+    n = _lanes(like)
+    if n is not None and normal.shape[1] != n:
+        raise ValueError(f"{what}: expected {n} normals, got {normal.shape[1]}")
+    if normal.shape[1] > 1 and normal.stride(1) != 1:
+        raise ValueError(f"{what}: rows must be contiguous")
+    if not normal.is_cuda:
+        raise TypeError(f"{what}: expected a CUDA tensor, got one on {normal.device}")
+    first = like[0] if isinstance(like, (tuple, list)) and len(like) > 0 else like
+    if isinstance(first, torch.Tensor) and first.is_cuda and first.device != normal.device:
+        raise TypeError(f"{what}: must live on {first.device}, got {normal.device}")
+    return normal[0].data_ptr(), normal[1].data_ptr(), normal[2].data_ptr()
+
+
+def _frame_call(fn_name, normal, v, mask, stream):
+    torch = _torch()
+    nptr = _normal_rows(normal, v)
+    if _is_f64(v):
+        raise TypeError("shading frames: floatRGB only (float32 tensors)")
+    x, y, z, n = _soa(v, what="v")
+    mptr, _keep = _mask_ptr(mask, n)
+    r = torch.empty((3, n), dtype=torch.float32, device=_device(v))
+    _on_stream(stream, _keep, r)
+    _lib.check(getattr(_lib.load(), fn_name)(*nptr, x, y, z, mptr, n, r[0].data_ptr(), r[1].data_ptr(),
+                                              r[2].data_ptr(), _stream_ptr(stream)))
+    return r
+
+
+def to_local(normal, v, mask=None, *, stream=None):
+    """World-space vectors v (3, N) in the shading frame of one normal per lane (bbm_hip_frame_to_local): the
+    reference's toLocalShadingFrame, transpose(toGlobalShadingFrame(normal)) v.  normal: (3, N) float32, any length
+    per normal; a lane whose normal is (about) zero, and a lane with mask == 0, gets (0, 0, 0).  -> (3, N)."""
+    return _frame_call("bbm_hip_frame_to_local", normal, v, mask, stream)
+
+
+def to_global(normal, v, mask=None, *, stream=None):
+    """Local vectors v (3, N) in world space (bbm_hip_frame_to_global): toGlobalShadingFrame(normal) v; see to_local."""
+    return _frame_call("bbm_hip_frame_to_global", normal, v, mask, stream)
+
+
 def _device(t):
     """The device of a (3, N) tensor or of a tuple of rows."""
     return (t[0] if isinstance(t, (tuple, list)) else t).device
@@ -527,19 +583,25 @@ class BsdfModel:
         return BsdfSample(d, p, f)
 
     def sample_eval(self, out, xi, component=bsdf_flag.All, unit=unit_t.Radiance, mask=None, *, value=True,
-                    weight=True, stream=None, exact=None):
+                    weight=True, stream=None, exact=None, normal=None):
         """One BSDF call per bounce in one launch (bbm_hip_sample_eval): -> (BsdfSample, value, weight).  The sample is
         sample(out, xi)'s, value (3, N) is eval_pdf(sample.direction, out)[0] and weight (3, N) is
         value * direction_z / pdf where pdf > epsilon(float32), else 0 -- each bit for bit what the staged calls give,
         without the sampled direction's round trip through memory.  value=False / weight=False: that group is not
-        stored and None is returned for it.  floatRGB only."""
+        stored and None is returned for it.  floatRGB only.
+        normal: a (3, N) float32 tensor of shading normals selects the world-space call (bbm_hip_sample_eval_world):
+        `out` and the returned direction are in world space, everything else is what to_local(normal, out), this call
+        and to_global(normal, direction) give in sequence (the weight's cosine is the local direction's)."""
+        nptr = None if normal is None else _normal_rows(normal, out)
         ox, oy, oz, n, x0, x1 = _sample_eval_inputs(out, xi)
         mptr, _keep = _mask_ptr(mask, n)
         outs = _sample_eval_outputs(n, x0.device, value, weight)
         _on_stream(stream, _keep, *outs)
         d, p, f, v, w = outs
-        _lib.check(_lib.load().bbm_hip_sample_eval(
-            self._call_id(exact), self._pptr(), self._params.size, ox, oy, oz, x0.data_ptr(), x1.data_ptr(), mptr, n,
+        lib = _lib.load()
+        fn, pre = (lib.bbm_hip_sample_eval, ()) if nptr is None else (lib.bbm_hip_sample_eval_world, nptr)
+        _lib.check(fn(
+            self._call_id(exact), self._pptr(), self._params.size, *pre, ox, oy, oz, x0.data_ptr(), x1.data_ptr(), mptr, n,
             int(component), int(unit), d[0].data_ptr(), d[1].data_ptr(), d[2].data_ptr(), p.data_ptr(), f.data_ptr(),
             *_row_ptrs(v), *_row_ptrs(w), _stream_ptr(stream)))
         return BsdfSample(d, p, f), v, w
@@ -870,15 +932,22 @@ class AggregateModel:
         return BsdfSample(d, p, f)
 
     def sample_eval(self, out, xi, component=bsdf_flag.All, unit=unit_t.Radiance, mask=None, *, value=True,
-                    weight=True, stream=None, exact=None):
+                    weight=True, stream=None, exact=None, normal=None):
         """BsdfModel.sample_eval for a composed or runtime tree -- staged: a tree has no fused kernel, so this runs
         the tree's own sample and eval_pdf on the GPU (two launches, the direction goes through memory) and forms
         the weight with torch float32 ops under the same rule (value * direction_z / pdf where pdf > epsilon, else
         0).  -> (BsdfSample, value or None, weight or None).  floatRGB only; a tree has no exact mode of its own, so
-        exact must be None."""
+        exact must be None.  normal: world space, staged as well -- to_local(normal, out), the above, then
+        to_global(normal, direction)."""
         torch = _torch()
         if exact is not None:
             raise NotImplementedError("sample_eval: composed aggregates follow the process-wide mode (exact=None)")
+        if normal is not None:
+            _normal_rows(normal, out)
+            _sample_eval_inputs(out, xi)
+            s, v, w = self.sample_eval(to_local(normal, out, mask, stream=stream), xi, component, unit, mask,
+                                       value=value, weight=weight, stream=stream)
+            return BsdfSample(to_global(normal, s.direction, mask, stream=stream), s.pdf, s.flag), v, w
         _sample_eval_inputs(out, xi)
         s = self.sample(out, xi, component, unit, mask, stream=stream)
         if not (value or weight):
@@ -1080,9 +1149,11 @@ class MaterialTable:
         return BsdfSample(d, p, f)
 
     def sample_eval(self, out, xi, component=bsdf_flag.All, unit=unit_t.Radiance, mask=None, *, material,
-                    value=True, weight=True, stream=None, exact=None):
+                    value=True, weight=True, stream=None, exact=None, normal=None):
         """BsdfModel.sample_eval with a material per lane (bbm_hip_sample_eval_table): lane i gets what the table's
-        sample followed by its eval_pdf at the sampled direction returns for material[i], and the weight."""
+        sample followed by its eval_pdf at the sampled direction returns for material[i], and the weight.  normal:
+        as BsdfModel.sample_eval's (bbm_hip_sample_eval_table_world)."""
+        nptr = None if normal is None else _normal_rows(normal, out)
         ox, oy, oz, n, x0, x1 = _sample_eval_inputs(out, xi)
         h = self._live()
         dev = x0.device
@@ -1091,8 +1162,10 @@ class MaterialTable:
         outs = _sample_eval_outputs(n, dev, value, weight)
         _on_stream(stream, _keep, material, *outs)
         d, p, f, v, w = outs
-        _lib.check(_lib.load().bbm_hip_sample_eval_table(
-            h, self._flags(exact), idx, ox, oy, oz, x0.data_ptr(), x1.data_ptr(), mptr, n, int(component), int(unit),
+        lib = _lib.load()
+        fn, pre = (lib.bbm_hip_sample_eval_table, ()) if nptr is None else (lib.bbm_hip_sample_eval_table_world, nptr)
+        _lib.check(fn(
+            h, self._flags(exact), idx, *pre, ox, oy, oz, x0.data_ptr(), x1.data_ptr(), mptr, n, int(component), int(unit),
             d[0].data_ptr(), d[1].data_ptr(), d[2].data_ptr(), p.data_ptr(), f.data_ptr(), *_row_ptrs(v),
             *_row_ptrs(w), _stream_ptr(stream)))
         return BsdfSample(d, p, f), v, w

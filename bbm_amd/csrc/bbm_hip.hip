@@ -285,6 +285,7 @@ int sample_eval_args(const float* out_x, const float* out_y, const float* out_z,
   if ((wr || wg || wb) && (!wr || !wg || !wb))
     return fail(BBM_HIP_ERR_INVALID_ARG, "weight output: give wr, wg and wb or none");
   a.r = r; a.g = g; a.b = b; a.wr = wr; a.wg = wg; a.wb = wb;
+  a.nx = a.ny = a.nz = nullptr;        // the world-space calls set them
   return BBM_HIP_OK;
 }
 
@@ -379,6 +380,32 @@ int bbm_hip_sample(int model_id, const float* params, int nparams,
   return e->run.sample(a, static_cast<hipStream_t>(stream));
 }
 
+// world: the normal pointers are the call's (bbm_hip_sample_eval_world), else they are not looked at
+static int sample_eval_common(bool world, int model_id, const float* params, int nparams,
+                              const float* nx, const float* ny, const float* nz,
+                              const float* out_x, const float* out_y, const float* out_z,
+                              const float* xi0, const float* xi1,
+                              const uint8_t* mask, size_t n, uint32_t component,
+                              float* dir_x, float* dir_y, float* dir_z, float* pdf, uint32_t* flag,
+                              float* r, float* g, float* b, float* wr, float* wg, float* wb, void* stream)
+{
+  const CallExactScope mode_scope(model_id);
+  EvalArgs tmp;
+  const ModelEntry* e;
+  int rc = prepare(model_id, params, nparams, n, tmp, e);
+  if (rc) return rc;
+  if (n == 0) return BBM_HIP_OK;
+  if (world && (rc = check_dirs(nx, ny, nz, "normal"))) return rc;
+  SampleEvalArgs a;
+  if ((rc = sample_eval_args(out_x, out_y, out_z, xi0, xi1, mask, n, component, dir_x, dir_y, dir_z, pdf, flag,
+                             r, g, b, wr, wg, wb, a)))
+    return rc;
+  a.s.p = tmp.p;
+  if (!world) return e->run.sample_eval(a, static_cast<hipStream_t>(stream));
+  a.nx = nx; a.ny = ny; a.nz = nz;
+  return e->run.sample_eval_world(a, static_cast<hipStream_t>(stream));
+}
+
 int bbm_hip_sample_eval(int model_id, const float* params, int nparams,
                         const float* out_x, const float* out_y, const float* out_z,
                         const float* xi0, const float* xi1,
@@ -387,18 +414,50 @@ int bbm_hip_sample_eval(int model_id, const float* params, int nparams,
                         float* r, float* g, float* b, float* wr, float* wg, float* wb, void* stream)
 {
   (void)unit;
-  const CallExactScope mode_scope(model_id);
-  EvalArgs tmp;
-  const ModelEntry* e;
-  int rc = prepare(model_id, params, nparams, n, tmp, e);
-  if (rc) return rc;
+  return sample_eval_common(false, model_id, params, nparams, nullptr, nullptr, nullptr, out_x, out_y, out_z, xi0, xi1,
+                            mask, n, component, dir_x, dir_y, dir_z, pdf, flag, r, g, b, wr, wg, wb, stream);
+}
+
+int bbm_hip_sample_eval_world(int model_id, const float* params, int nparams,
+                              const float* nx, const float* ny, const float* nz,
+                              const float* out_x, const float* out_y, const float* out_z,
+                              const float* xi0, const float* xi1,
+                              const uint8_t* mask, size_t n, uint32_t component, uint32_t unit,
+                              float* dir_x, float* dir_y, float* dir_z, float* pdf, uint32_t* flag,
+                              float* r, float* g, float* b, float* wr, float* wg, float* wb, void* stream)
+{
+  (void)unit;
+  return sample_eval_common(true, model_id, params, nparams, nx, ny, nz, out_x, out_y, out_z, xi0, xi1,
+                            mask, n, component, dir_x, dir_y, dir_z, pdf, flag, r, g, b, wr, wg, wb, stream);
+}
+
+// ------------------------------------------------------------------------------- shading frames (frame.hpp)
+
+static int frame_common(bool to_local, const float* nx, const float* ny, const float* nz,
+                        const float* x, const float* y, const float* z, const uint8_t* mask, size_t n,
+                        float* rx, float* ry, float* rz, void* stream)
+{
   if (n == 0) return BBM_HIP_OK;
-  SampleEvalArgs a;
-  if ((rc = sample_eval_args(out_x, out_y, out_z, xi0, xi1, mask, n, component, dir_x, dir_y, dir_z, pdf, flag,
-                             r, g, b, wr, wg, wb, a)))
+  int rc;
+  if ((rc = check_dirs(nx, ny, nz, "normal")) || (rc = check_dirs(x, y, z, "input")) ||
+      (rc = check_dirs(rx, ry, rz, "output")))
     return rc;
-  a.s.p = tmp.p;
-  return e->run.sample_eval(a, static_cast<hipStream_t>(stream));
+  const FrameArgs a{nx, ny, nz, x, y, z, mask, n, rx, ry, rz};
+  return frame_launch(a, to_local, static_cast<hipStream_t>(stream));
+}
+
+int bbm_hip_frame_to_local(const float* nx, const float* ny, const float* nz,
+                           const float* x, const float* y, const float* z, const uint8_t* mask, size_t n,
+                           float* lx, float* ly, float* lz, void* stream)
+{
+  return frame_common(true, nx, ny, nz, x, y, z, mask, n, lx, ly, lz, stream);
+}
+
+int bbm_hip_frame_to_global(const float* nx, const float* ny, const float* nz,
+                            const float* lx, const float* ly, const float* lz, const uint8_t* mask, size_t n,
+                            float* x, float* y, float* z, void* stream)
+{
+  return frame_common(false, nx, ny, nz, lx, ly, lz, mask, n, x, y, z, stream);
 }
 
 int bbm_hip_reflectance(int model_id, const float* params, int nparams,
@@ -648,19 +707,20 @@ int bbm_hip_sample_table(const bbm_hip_table* t, int call_flags, const uint32_t*
   return t->e->run.sample_tab(a, static_cast<hipStream_t>(stream));
 }
 
-int bbm_hip_sample_eval_table(const bbm_hip_table* t, int call_flags, const uint32_t* material,
-                              const float* out_x, const float* out_y, const float* out_z,
-                              const float* xi0, const float* xi1,
-                              const uint8_t* mask, size_t n, uint32_t component, uint32_t unit,
-                              float* dir_x, float* dir_y, float* dir_z, float* pdf, uint32_t* flag,
-                              float* r, float* g, float* b, float* wr, float* wg, float* wb, void* stream)
+static int sample_eval_table_common(bool world, const bbm_hip_table* t, int call_flags, const uint32_t* material,
+                                    const float* nx, const float* ny, const float* nz,
+                                    const float* out_x, const float* out_y, const float* out_z,
+                                    const float* xi0, const float* xi1,
+                                    const uint8_t* mask, size_t n, uint32_t component,
+                                    float* dir_x, float* dir_y, float* dir_z, float* pdf, uint32_t* flag,
+                                    float* r, float* g, float* b, float* wr, float* wg, float* wb, void* stream)
 {
-  (void)unit;
   int rc = table_call(t, call_flags, n, material);
   if (rc) return rc;
   if (!t->e->run.sample_eval_tab)
     return fail(BBM_HIP_ERR_UNSUPPORTED, std::string(t->e->name) + ": no material-table kernels");
   if (n == 0) return BBM_HIP_OK;
+  if (world && (rc = check_dirs(nx, ny, nz, "normal"))) return rc;
   const CallExactScope mode_scope(call_flags);
   SampleEvalTabArgs a;
   if ((rc = sample_eval_args(out_x, out_y, out_z, xi0, xi1, mask, n, component, dir_x, dir_y, dir_z, pdf, flag,
@@ -669,7 +729,34 @@ int bbm_hip_sample_eval_table(const bbm_hip_table* t, int call_flags, const uint
   // the block form sample and eval + pdf read (host_params applied)
   a.e.s.p = t->first_prepared;
   a.src = {t->prepared, material, t->count};
-  return t->e->run.sample_eval_tab(a, static_cast<hipStream_t>(stream));
+  if (!world) return t->e->run.sample_eval_tab(a, static_cast<hipStream_t>(stream));
+  a.e.nx = nx; a.e.ny = ny; a.e.nz = nz;
+  return t->e->run.sample_eval_tab_world(a, static_cast<hipStream_t>(stream));
+}
+
+int bbm_hip_sample_eval_table(const bbm_hip_table* t, int call_flags, const uint32_t* material,
+                              const float* out_x, const float* out_y, const float* out_z,
+                              const float* xi0, const float* xi1,
+                              const uint8_t* mask, size_t n, uint32_t component, uint32_t unit,
+                              float* dir_x, float* dir_y, float* dir_z, float* pdf, uint32_t* flag,
+                              float* r, float* g, float* b, float* wr, float* wg, float* wb, void* stream)
+{
+  (void)unit;
+  return sample_eval_table_common(false, t, call_flags, material, nullptr, nullptr, nullptr, out_x, out_y, out_z, xi0,
+                                  xi1, mask, n, component, dir_x, dir_y, dir_z, pdf, flag, r, g, b, wr, wg, wb, stream);
+}
+
+int bbm_hip_sample_eval_table_world(const bbm_hip_table* t, int call_flags, const uint32_t* material,
+                                    const float* nx, const float* ny, const float* nz,
+                                    const float* out_x, const float* out_y, const float* out_z,
+                                    const float* xi0, const float* xi1,
+                                    const uint8_t* mask, size_t n, uint32_t component, uint32_t unit,
+                                    float* dir_x, float* dir_y, float* dir_z, float* pdf, uint32_t* flag,
+                                    float* r, float* g, float* b, float* wr, float* wg, float* wb, void* stream)
+{
+  (void)unit;
+  return sample_eval_table_common(true, t, call_flags, material, nx, ny, nz, out_x, out_y, out_z, xi0, xi1, mask, n,
+                                  component, dir_x, dir_y, dir_z, pdf, flag, r, g, b, wr, wg, wb, stream);
 }
 
 int bbm_hip_reflectance_table(const bbm_hip_table* t, int call_flags, const uint32_t* material,

@@ -21,7 +21,8 @@
 // entry points -> shade / accumulate / bin.  Same functions, same order: the same image bit for bit.
 #pragma once
 #include "math.hpp"
-#include "fit.hpp"     // sph_to_vec, phi_of, theta_of, cossin_cr
+#include "frame.hpp"
+#include "fit.hpp"    // sph_to_vec, phi_of, theta_of, cossin_cr
 #include "check.hpp"   // uniform2, check_base_key, check_key
 
 namespace bbmhip {
@@ -68,22 +69,11 @@ __device__ __forceinline__ bool sphere_pixel(uint32_t x, uint32_t y, uint32_t w,
   if (len < 1.0f) n.z = sqrt_nr(1.0f - len);
   else n = mk3(0.0f, 0.0f, 0.0f);
   in = out = mk3(0.0f, 0.0f, 0.0f);
-  const float nn = dot3(n, n);
-  if (!(nn > kEpsF)) return false;
-  // toGlobalShadingFrame: Z = normalize(n) = n * (1 / sqrt(|n|^2)).  The double literals (-1.0 / (sign + z),
-  // 1.0 + ...) widen one float operand, and one double operation rounded to float is the float operation
-  // (53 >= 2 x 24 + 2), so everything below is float arithmetic.
-  const float r = div_nr(1.0f, sqrt_nr(nn));
-  const v3 Z = mk3(n.x * r, n.y * r, n.z * r);
-  const float sign = copysignf(1.0f, Z.z);
-  const float a = div_nr(-1.0f, sign + Z.z);
-  const float b = (Z.x * Z.y) * a;
-  const v3 X = mk3(1.0f + ((sign * Z.x) * Z.x) * a, sign * b, (-sign) * Z.x);
-  const v3 Y = mk3(b, sign + (Z.y * Z.y) * a, -Z.y);
-  // transpose(mat3d(X, Y, Z)) * v: row r of the transpose is column r, one dot per row (core/mat.h:107-116)
-  const v3 view = mk3(0.0f, 0.0f, 1.0f);
-  in = mk3(dot3(X, light), dot3(Y, light), dot3(Z, light));
-  out = mk3(dot3(X, view), dot3(Y, view), dot3(Z, view));
+  // transpose(toGlobalShadingFrame(n)) * v (frame.hpp)
+  const Frame f = shading_frame(n);
+  if (!f.live) return false;
+  in = f.to_local(light);
+  out = f.to_local(mk3(0.0f, 0.0f, 1.0f));
   return true;
 }
 

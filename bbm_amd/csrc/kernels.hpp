@@ -1195,6 +1195,9 @@ struct Launchers
   // sample + eval + weight in one launch (sample_eval.hpp); the table twin null where there are no tables
   SampleEvalLauncher sample_eval;
   SampleEvalTabLauncher sample_eval_tab;
+  // the same in world space: per-lane shading frames inside the kernel (sample_eval.hpp, FRAME)
+  SampleEvalLauncher sample_eval_world;
+  SampleEvalTabLauncher sample_eval_tab_world;
 };
 template<class M> constexpr Launchers launchers()
 {
@@ -1204,10 +1207,12 @@ template<class M> constexpr Launchers launchers()
             &launch_reflectance_lanes<M, ReflVarArgs>,
             &table_prepare<M>, &launch_eval_pdf_lanes<M, EvalTabArgs>, &launch_sample_lanes<M, SampleTabArgs>,
             &launch_reflectance_lanes<M, ReflTabArgs>,
-            &launch_sample_eval<M>, &launch_sample_eval_tab<M>};
+            &launch_sample_eval<M>, &launch_sample_eval_tab<M>, &launch_sample_eval_world<M>,
+            &launch_sample_eval_tab_world<M>};
   else
     return {&launch_eval_pdf<M>, &launch_sample<M>, &launch_reflectance<M>, &launch_loss<M>, &launch_check<M>, &launch_image<M>,
-            nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &launch_sample_eval<M>, nullptr};
+            nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &launch_sample_eval<M>, nullptr,
+            &launch_sample_eval_world<M>, nullptr};
 }
 
 }  // namespace bbmhip

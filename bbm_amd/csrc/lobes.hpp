@@ -6,6 +6,7 @@
 // applied with selects, parameters are the flat parameter_values() vector.
 #pragma once
 #include "math.hpp"
+#include "frame.hpp"
 #include "diffuse.hpp"
 #include "microfacet.hpp"
 
@@ -23,17 +24,10 @@ __device__ __forceinline__ v3 to_global(v3 normal, v3 v)
 {
   // the normal is a model parameter (any vector a caller sets): the IEEE-style quotient keeps the reference's
   // results at the edges (|n|^2 = inf -> 0 components, not NaN); directions use the fast normalize3
+  // (the library root here, where the shading normal of frame.hpp's shading_frame takes sqrt_nr; no liveness test:
+  // a lobe's axis is used whatever its length)
   const float rn = div_nr(1.0f, sqrtf(dot3(normal, normal)));
-  const v3 Z = mk3(normal.x * rn, normal.y * rn, normal.z * rn);
-  const float sign = copysignf(1.0f, Z.z);
-  const float a = div_nr(-1.0f, sign + Z.z);          // -1.0 / (sign + z): one double op on floats
-  const float b = Z.x * Z.y * a;
-  const v3 X = mk3(1.0f + sign * Z.x * Z.x * a, sign * b, -sign * Z.x);   // 1.0 + f: idem
-  const v3 Y = mk3(b, sign + Z.y * Z.y * a, -Z.y);
-  // mat3d * vec: row r = (X[r], Y[r], Z[r]) dotted with v (core/mat.h:107-116)
-  return mk3(((0.0f + X.x * v.x) + Y.x * v.y) + Z.x * v.z,
-             ((0.0f + X.y * v.x) + Y.y * v.y) + Z.y * v.z,
-             ((0.0f + X.z * v.x) + Y.z * v.y) + Z.z * v.z);
+  return frame_scaled(normal, rn, true).to_global(v);
 }
 
 __device__ __forceinline__ bool xi_valid(float xi0, float xi1)

@@ -195,6 +195,46 @@ template<> struct sample_eval_tab_quad<AggLowMicrofacetM, true> { static constex
 template<> struct sample_eval_tab_quad<AggNganCookTorranceM, false> { static constexpr bool value = false; };
 template<> struct sample_eval_tab_quad<AggNganCookTorranceM, true> { static constexpr bool value = false; };
 
+// The world-space kernels (FRAME), judged again on top of the above: a quad kernel that spills with
+// the frames in registers -- to scratch, or to AGPRs at half the local kernel's waves (the He family, EPD's table
+// kernel) -- where the row's one-lane world kernel does not.  U: the uniform call, T: the table call.
+#define BBM_HIP_WORLD_ONE_LANE_UD(M) template<> struct sample_eval_world_quad<M, false> { static constexpr bool value = false; };
+#define BBM_HIP_WORLD_ONE_LANE_UE(M) template<> struct sample_eval_world_quad<M, true> { static constexpr bool value = false; };
+#define BBM_HIP_WORLD_ONE_LANE_TD(M) template<> struct sample_eval_tab_world_quad<M, false> { static constexpr bool value = false; };
+#define BBM_HIP_WORLD_ONE_LANE_TE(M) template<> struct sample_eval_tab_world_quad<M, true> { static constexpr bool value = false; };
+#define BBM_HIP_WORLD_ONE_LANE_U(M) BBM_HIP_WORLD_ONE_LANE_UD(M) BBM_HIP_WORLD_ONE_LANE_UE(M)
+#define BBM_HIP_WORLD_ONE_LANE_T(M) BBM_HIP_WORLD_ONE_LANE_TD(M) BBM_HIP_WORLD_ONE_LANE_TE(M)
+BBM_HIP_WORLD_ONE_LANE_U(HeM)
+BBM_HIP_WORLD_ONE_LANE_U(HeWestinM)
+BBM_HIP_WORLD_ONE_LANE_U(HeHolzschuchM)
+BBM_HIP_WORLD_ONE_LANE_U(NganHeM)
+BBM_HIP_WORLD_ONE_LANE_U(AggNganHeM)
+BBM_HIP_WORLD_ONE_LANE_U(AggGGXM)
+BBM_HIP_WORLD_ONE_LANE_U(AggNganWardM)
+BBM_HIP_WORLD_ONE_LANE_U(AggNganWardDuerM)
+BBM_HIP_WORLD_ONE_LANE_U(LowSmooth)
+BBM_HIP_WORLD_ONE_LANE_U(Merl)
+BBM_HIP_WORLD_ONE_LANE_UE(CookTorranceWalterM)
+BBM_HIP_WORLD_ONE_LANE_UE(CookTorranceHeitzM)
+BBM_HIP_WORLD_ONE_LANE_TE(CookTorranceM)
+BBM_HIP_WORLD_ONE_LANE_TE(NganCookTorranceM)
+BBM_HIP_WORLD_ONE_LANE_T(EpdM)
+BBM_HIP_WORLD_ONE_LANE_T(Bagher)
+BBM_HIP_WORLD_ONE_LANE_T(ASM)
+BBM_HIP_WORLD_ONE_LANE_T(ASFullM)
+BBM_HIP_WORLD_ONE_LANE_T(LowASM)
+BBM_HIP_WORLD_ONE_LANE_T(NganASM)
+BBM_HIP_WORLD_ONE_LANE_T(NganLafortuneM)
+BBM_HIP_WORLD_ONE_LANE_T(AggBagherM)
+BBM_HIP_WORLD_ONE_LANE_TE(AggCookTorranceM)
+BBM_HIP_WORLD_ONE_LANE_T(AggGGXM)
+BBM_HIP_WORLD_ONE_LANE_T(AggLowASM)
+BBM_HIP_WORLD_ONE_LANE_TD(AggLowMicrofacetM)
+BBM_HIP_WORLD_ONE_LANE_T(AggLowSmoothM)
+BBM_HIP_WORLD_ONE_LANE_T(AggNganASM)
+BBM_HIP_WORLD_ONE_LANE_T(AggPhongM)
+BBM_HIP_WORLD_ONE_LANE_T(AggNganLafortuneM)
+
 }  // namespace bbmhip
 
 // X(composition) per instantiation unit
@@ -228,7 +268,9 @@ template<> struct sample_eval_tab_quad<AggNganCookTorranceM, true> { static cons
   template int launch_sample_lanes<M, SampleTabArgs>(const SampleTabArgs&, hipStream_t);       \
   template int launch_reflectance_lanes<M, ReflTabArgs>(const ReflTabArgs&, hipStream_t);    \
   template int launch_sample_eval<M>(const SampleEvalArgs&, hipStream_t);     \
-  template int launch_sample_eval_tab<M>(const SampleEvalTabArgs&, hipStream_t);
+  template int launch_sample_eval_tab<M>(const SampleEvalTabArgs&, hipStream_t); \
+  template int launch_sample_eval_world<M>(const SampleEvalArgs&, hipStream_t); \
+  template int launch_sample_eval_tab_world<M>(const SampleEvalTabArgs&, hipStream_t);
 #define BBM_HIP_EXTERN(M)                                                       \
   extern template int launch_eval_pdf<M>(const EvalArgs&, int, hipStream_t);    \
   extern template int launch_sample<M>(const SampleArgs&, hipStream_t);         \
@@ -244,4 +286,6 @@ template<> struct sample_eval_tab_quad<AggNganCookTorranceM, true> { static cons
   extern template int launch_sample_lanes<M, SampleTabArgs>(const SampleTabArgs&, hipStream_t); \
   extern template int launch_reflectance_lanes<M, ReflTabArgs>(const ReflTabArgs&, hipStream_t); \
   extern template int launch_sample_eval<M>(const SampleEvalArgs&, hipStream_t); \
-  extern template int launch_sample_eval_tab<M>(const SampleEvalTabArgs&, hipStream_t);
+  extern template int launch_sample_eval_tab<M>(const SampleEvalTabArgs&, hipStream_t); \
+  extern template int launch_sample_eval_world<M>(const SampleEvalArgs&, hipStream_t); \
+  extern template int launch_sample_eval_tab_world<M>(const SampleEvalTabArgs&, hipStream_t);

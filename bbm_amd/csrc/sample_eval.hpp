@@ -13,6 +13,11 @@
 // output array, grid-stride up to max_blocks(), a scalar tail.  The mask and whether the value and the weight group
 // are stored are runtime, wave-uniform arguments, so a row has one quad and one one-lane kernel, times the exact
 // variant where it has one.  Unaligned arrays (and the rows sample_eval_quad excludes) take one lane per thread.
+//
+// FRAME (a compile-time parameter of the four kernels): the world-space calls bbm_hip_sample_eval_world and
+// bbm_hip_sample_eval_table_world -- `out` and the direction in world space, one shading normal per lane, the frame
+// (frame.hpp) built and applied in registers (frame_sample_eval).  Without it the kernels are the
+// local calls' and hold nothing of the frame.
 #pragma once
 
 namespace bbmhip {
@@ -22,6 +27,7 @@ struct SampleEvalArgs
   SampleArgs s;                       // the inputs, and dir / pdf / flag (required)
   float* r; float* g; float* b;       // value = eval(dir, out); all null: not stored
   float* wr; float* wg; float* wb;    // weight; all null: not stored
+  const float* nx; const float* ny; const float* nz;   // the world-space calls' shading normal per lane, else null
 };
 struct SampleEvalTabArgs : LaneArgs<SampleEvalArgs, TabRef> {};     // e.s.p: the fallback block (table.hpp)
 
@@ -60,19 +66,53 @@ __device__ __forceinline__ void sample_weight(const float* rgb, float dz, float 
   for (int c = 0; c < 3; ++c) w[c] = (pdf > kEpsF) ? (rgb[c] * dz) / pdf : 0.0f;
 }
 
-template<bool EXACT, class Model>
-__device__ __forceinline__ void one_sample_eval(const Model& m, const SampleEvalArgs& a, uint64_t i, bool active)
+// The world-space lane (FRAME; bbm_hip_sample_eval_world): `out` and the returned direction are in
+// world space, the model runs in the shading frame of the lane's normal (frame.hpp), which stays in registers.
+// Lane i returns what frame_to_local, the local call and frame_to_global return for it in sequence, bit for bit: a
+// lane that is masked (`on` false) or whose normal is not live runs the model with component 0 at out = 0, as a
+// masked lane of the local call after frame_to_local's 0, and its direction is frame_to_global's 0; `src_live`
+// (a table lane's material index in range) switches the component alone, as in the local table call.  cosz is the
+// local dir.z, the weight's cosine.  Without FRAME this is model_sample_eval and nothing else.
+template<bool FRAME, bool EXACT, class Model>
+__device__ __forceinline__ void frame_sample_eval(const Model& m, v3 normal, v3 out, float xi0, float xi1, bool on,
+                                                  bool src_live, uint32_t component, v3& dir, float& cosz, float* rgb,
+                                                  float& pdf, uint32_t& flag)
+{
+  if constexpr (FRAME)
+  {
+    const Frame f = shading_frame(normal);
+    const bool in_frame = on && f.live;
+    const v3 lo = f.to_local(out);
+    v3 d;
+    model_sample_eval<EXACT>(m, in_frame ? lo : mk3(0.0f, 0.0f, 0.0f), xi0, xi1,
+                             (in_frame && src_live) ? component : 0u, d, rgb, pdf, flag);
+    cosz = d.z;
+    const v3 g = f.to_global(d);
+    dir = in_frame ? g : mk3(0.0f, 0.0f, 0.0f);
+  }
+  else
+  {
+    model_sample_eval<EXACT>(m, out, xi0, xi1, (on && src_live) ? component : 0u, dir, rgb, pdf, flag);
+    cosz = dir.z;
+  }
+}
+
+// `on`: the lane's mask; `src_live`: see frame_sample_eval (true for the uniform call)
+template<bool FRAME, bool EXACT, class Model>
+__device__ __forceinline__ void one_sample_eval(const Model& m, const SampleEvalArgs& a, uint64_t i, bool on,
+                                                bool src_live)
 {
   const SampleArgs& s = a.s;
-  v3 d; float rgb[3], pdf; uint32_t f;
-  model_sample_eval<EXACT>(m, mk3(s.ox[i], s.oy[i], s.oz[i]), s.xi0[i], s.xi1[i], active ? s.component : 0u, d, rgb,
-                           pdf, f);
+  v3 d; float rgb[3], pdf, cz; uint32_t f;
+  const v3 nrm = FRAME ? mk3(a.nx[i], a.ny[i], a.nz[i]) : mk3(0.0f, 0.0f, 0.0f);
+  frame_sample_eval<FRAME, EXACT>(m, nrm, mk3(s.ox[i], s.oy[i], s.oz[i]), s.xi0[i], s.xi1[i], on, src_live,
+                                  s.component, d, cz, rgb, pdf, f);
   s.dx[i] = d.x; s.dy[i] = d.y; s.dz[i] = d.z; s.pdf[i] = pdf; s.flag[i] = f;
   if (a.r) { a.r[i] = rgb[0]; a.g[i] = rgb[1]; a.b[i] = rgb[2]; }
   if (a.wr)
   {
     float w[3];
-    sample_weight(rgb, d.z, pdf, w);
+    sample_weight(rgb, cz, pdf, w);
     a.wr[i] = w[0]; a.wg[i] = w[1]; a.wb[i] = w[2];
   }
 }
@@ -84,14 +124,29 @@ __device__ __forceinline__ void one_sample_eval(const Model& m, const SampleEval
 // Specialised in models.hpp.
 template<class Model, bool EXACT> struct sample_eval_quad { static constexpr bool value = true; };
 template<class Model, bool EXACT> struct sample_eval_tab_quad { static constexpr bool value = true; };
+// The world-space kernels hold the frame's nine floats across the model call, so they are judged again, on top of
+// the local kernels' choice.  Specialised in models.hpp.
+template<class Model, bool EXACT> struct sample_eval_world_quad : sample_eval_quad<Model, EXACT> {};
+template<class Model, bool EXACT> struct sample_eval_tab_world_quad : sample_eval_tab_quad<Model, EXACT> {};
+template<bool FRAME, class Model, bool EXACT> constexpr bool sample_eval_use_quad()
+{
+  if constexpr (FRAME) return sample_eval_world_quad<Model, EXACT>::value;
+  else return sample_eval_quad<Model, EXACT>::value;
+}
+template<bool FRAME, class Model, bool EXACT> constexpr bool sample_eval_tab_use_quad()
+{
+  if constexpr (FRAME) return sample_eval_tab_world_quad<Model, EXACT>::value;
+  else return sample_eval_tab_quad<Model, EXACT>::value;
+}
 
 // Occupancy: the chain is k_check's reflectance test (sample, eval, the weight), so its choice is the starting point
 // (check_waves: 4 waves per SIMD, the compiler's own for the He family and EPD) -- not measured for this kernel.
 #define BBM_HIP_SAMPLE_EVAL_ATTR(Model) __attribute__((amdgpu_waves_per_eu(check_waves<Model>::value, 8)))
 
 // One quad's stores, t the quad's index in every array; the weights are formed only where they are stored.
+// cz: the weight's cosine, the local dir.z (dz itself in the local kernels).
 __device__ __forceinline__ void store_sample_eval(const SampleEvalArgs& a, uint64_t t, const float* dx,
-                                                  const float* dy, const float* dz, const float* pd,
+                                                  const float* dy, const float* dz, const float* cz, const float* pd,
                                                   const uint32_t* fl, const float (*rgb)[4])
 {
   const SampleArgs& s = a.s;
@@ -115,7 +170,7 @@ __device__ __forceinline__ void store_sample_eval(const SampleEvalArgs& a, uint6
     {
       const float f[3] = {rgb[0][j], rgb[1][j], rgb[2][j]};
       float wj[3];
-      sample_weight(f, dz[j], pd[j], wj);
+      sample_weight(f, cz[j], pd[j], wj);
       w[0][j] = wj[0]; w[1][j] = wj[1]; w[2][j] = wj[2];
     }
     st4<true>(a.wr, t, w[0][0], w[0][1], w[0][2], w[0][3]);
@@ -126,7 +181,8 @@ __device__ __forceinline__ void store_sample_eval(const SampleEvalArgs& a, uint6
 
 // 4 lanes per thread-iteration: 5 x 16-byte loads (out xyz, xi0, xi1), 5 + 3 + 3 x 16-byte stores.  Requires every
 // array 16-byte aligned and the mask 4-byte aligned (checked on the host); the n % 4 tail runs scalar.
-template<class Model, bool EXACT>
+// FRAME: three more loads (the normal).
+template<class Model, bool EXACT, bool FRAME>
 __global__ __launch_bounds__(kBlock) BBM_HIP_SAMPLE_EVAL_ATTR(Model) void k_sample_eval_v4(SampleEvalArgs a)
 {
   math_tables_init();
@@ -138,46 +194,49 @@ __global__ __launch_bounds__(kBlock) BBM_HIP_SAMPLE_EVAL_ATTR(Model) void k_samp
   {
     const float4 ox = ld4<true>(s.ox, t), oy = ld4<true>(s.oy, t), oz = ld4<true>(s.oz, t);
     const float4 x0 = ld4<true>(s.xi0, t), x1 = ld4<true>(s.xi1, t);
+    float4 wx = {}, wy = {}, wz = {};
+    if constexpr (FRAME) { wx = ld4<true>(a.nx, t); wy = ld4<true>(a.ny, t); wz = ld4<true>(a.nz, t); }
     const uint32_t mk = s.mask ? reinterpret_cast<const uint32_t*>(s.mask)[t] : 0x01010101u;
     const float onx[4] = {ox.x, ox.y, ox.z, ox.w}, ony[4] = {oy.x, oy.y, oy.z, oy.w}, onz[4] = {oz.x, oz.y, oz.z, oz.w};
     const float u0[4] = {x0.x, x0.y, x0.z, x0.w}, u1[4] = {x1.x, x1.y, x1.z, x1.w};
-    float dx[4], dy[4], dz[4], pd[4], rgb[3][4];
+    const float nnx[4] = {wx.x, wx.y, wx.z, wx.w}, nny[4] = {wy.x, wy.y, wy.z, wy.w}, nnz[4] = {wz.x, wz.y, wz.z, wz.w};
+    float dx[4], dy[4], dz[4], cz[4], pd[4], rgb[3][4];
     uint32_t fl[4];
 #pragma unroll
     for (int j = 0; j < 4; ++j)
     {
       v3 d;
       float f[3];
-      const uint32_t comp = ((mk >> (8 * j)) & 0xffu) ? s.component : 0u;
-      model_sample_eval<EXACT>(m, mk3(onx[j], ony[j], onz[j]), u0[j], u1[j], comp, d, f, pd[j], fl[j]);
+      frame_sample_eval<FRAME, EXACT>(m, mk3(nnx[j], nny[j], nnz[j]), mk3(onx[j], ony[j], onz[j]), u0[j], u1[j],
+                                      ((mk >> (8 * j)) & 0xffu) != 0, true, s.component, d, cz[j], f, pd[j], fl[j]);
       dx[j] = d.x; dy[j] = d.y; dz[j] = d.z;
 #pragma unroll
       for (int c = 0; c < 3; ++c) rgb[c][j] = f[c];
     }
-    store_sample_eval(a, t, dx, dy, dz, pd, fl, rgb);
+    store_sample_eval(a, t, dx, dy, dz, cz, pd, fl, rgb);
   }
   if (blockIdx.x == 0 && threadIdx.x < (s.n & 3))
   {
     const uint64_t i = (n4 << 2) + threadIdx.x;
-    one_sample_eval<EXACT>(m, a, i, s.mask ? (s.mask[i] != 0) : true);
+    one_sample_eval<FRAME, EXACT>(m, a, i, s.mask ? (s.mask[i] != 0) : true, true);
   }
 }
 
 // Scalar path for unaligned arrays.
-template<class Model, bool EXACT>
+template<class Model, bool EXACT, bool FRAME>
 __global__ __launch_bounds__(kBlock) BBM_HIP_SAMPLE_EVAL_ATTR(Model) void k_sample_eval_v1(SampleEvalArgs a)
 {
   math_tables_init();
   const Model m(a.s.p.v);
   const uint64_t stride = uint64_t(gridDim.x) * kBlock;
   for (uint64_t i = uint64_t(blockIdx.x) * kBlock + threadIdx.x; i < a.s.n; i += stride)
-    one_sample_eval<EXACT>(m, a, i, a.s.mask ? (a.s.mask[i] != 0) : true);
+    one_sample_eval<FRAME, EXACT>(m, a, i, a.s.mask ? (a.s.mask[i] != 0) : true, true);
 }
 
 // Material tables: the same lane behind a lane-parameter source (lanes.hpp; instantiated for TabRef only, there is
 // no per-row entry point).  S: the slot count of the model the table was made for (Model may be its exact-mode
 // sampling twin).  One model is live at a time.
-template<class Model, int S, bool EXACT, class A>
+template<class Model, int S, bool EXACT, bool FRAME, class A>
 __device__ __forceinline__ void lane_one_sample_eval(const A& a, uint64_t i)
 {
   const SampleArgs& s = a.e.s;
@@ -185,14 +244,12 @@ __device__ __forceinline__ void lane_one_sample_eval(const A& a, uint64_t i)
   ParamBlock q;
   a.src.template lane_block<S>(s.p, l, i, q);
   const Model m(q.v);
-  bool active = s.mask ? (s.mask[i] != 0) : true;
-  active = active && a.src.lane_live(l);
-  one_sample_eval<EXACT>(m, a.e, i, active);
+  one_sample_eval<FRAME, EXACT>(m, a.e, i, s.mask ? (s.mask[i] != 0) : true, a.src.lane_live(l));
 }
 
 // Four lanes per thread; every float array and the source's own 16-byte aligned, the mask 4-byte aligned.  A full
 // grid, as the other per-lane kernels.
-template<class Model, int S, bool EXACT, class A>
+template<class Model, int S, bool EXACT, bool FRAME, class A>
 __global__ __launch_bounds__(kBlock) BBM_HIP_SAMPLE_EVAL_ATTR(Model) void k_seval_lane4(A a)
 {
   math_tables_init();
@@ -203,11 +260,14 @@ __global__ __launch_bounds__(kBlock) BBM_HIP_SAMPLE_EVAL_ATTR(Model) void k_seva
   {
     const float4 ox = ld4<true>(s.ox, t), oy = ld4<true>(s.oy, t), oz = ld4<true>(s.oz, t);
     const float4 x0 = ld4<true>(s.xi0, t), x1 = ld4<true>(s.xi1, t);
+    float4 wx = {}, wy = {}, wz = {};
+    if constexpr (FRAME) { wx = ld4<true>(a.e.nx, t); wy = ld4<true>(a.e.ny, t); wz = ld4<true>(a.e.nz, t); }
     const auto c = a.src.template load_quad<S>(t);
     const uint32_t mk = s.mask ? reinterpret_cast<const uint32_t*>(s.mask)[t] : 0x01010101u;
     const float onx[4] = {ox.x, ox.y, ox.z, ox.w}, ony[4] = {oy.x, oy.y, oy.z, oy.w}, onz[4] = {oz.x, oz.y, oz.z, oz.w};
     const float u0[4] = {x0.x, x0.y, x0.z, x0.w}, u1[4] = {x1.x, x1.y, x1.z, x1.w};
-    float dx[4], dy[4], dz[4], pd[4], rgb[3][4];
+    const float nnx[4] = {wx.x, wx.y, wx.z, wx.w}, nny[4] = {wy.x, wy.y, wy.z, wy.w}, nnz[4] = {wz.x, wz.y, wz.z, wz.w};
+    float dx[4], dy[4], dz[4], cz[4], pd[4], rgb[3][4];
     uint32_t fl[4];
 #pragma unroll
     for (int j = 0; j < 4; ++j)
@@ -217,27 +277,26 @@ __global__ __launch_bounds__(kBlock) BBM_HIP_SAMPLE_EVAL_ATTR(Model) void k_seva
       const Model m(q.v);
       v3 d;
       float f[3];
-      bool active = (mk >> (8 * j)) & 0xffu;
-      active = active && a.src.quad_live(c, j);
-      const uint32_t comp = active ? s.component : 0u;
-      model_sample_eval<EXACT>(m, mk3(onx[j], ony[j], onz[j]), u0[j], u1[j], comp, d, f, pd[j], fl[j]);
+      frame_sample_eval<FRAME, EXACT>(m, mk3(nnx[j], nny[j], nnz[j]), mk3(onx[j], ony[j], onz[j]), u0[j], u1[j],
+                                      ((mk >> (8 * j)) & 0xffu) != 0, a.src.quad_live(c, j), s.component, d, cz[j], f,
+                                      pd[j], fl[j]);
       dx[j] = d.x; dy[j] = d.y; dz[j] = d.z;
 #pragma unroll
       for (int c3 = 0; c3 < 3; ++c3) rgb[c3][j] = f[c3];
     }
-    store_sample_eval(a.e, t, dx, dy, dz, pd, fl, rgb);
+    store_sample_eval(a.e, t, dx, dy, dz, cz, pd, fl, rgb);
   }
   // tail
-  if (blockIdx.x == 0 && threadIdx.x < (s.n & 3)) lane_one_sample_eval<Model, S, EXACT>(a, (n4 << 2) + threadIdx.x);
+  if (blockIdx.x == 0 && threadIdx.x < (s.n & 3)) lane_one_sample_eval<Model, S, EXACT, FRAME>(a, (n4 << 2) + threadIdx.x);
 }
 
 // One lane per thread: unaligned arrays (and the rows sample_eval_tab_quad excludes).
-template<class Model, int S, bool EXACT, class A>
+template<class Model, int S, bool EXACT, bool FRAME, class A>
 __global__ __launch_bounds__(kBlock) BBM_HIP_SAMPLE_EVAL_ATTR(Model) void k_seval_lane1(A a)
 {
   math_tables_init();
   const uint64_t i = uint64_t(blockIdx.x) * kBlock + threadIdx.x;
-  if (i < a.e.s.n) lane_one_sample_eval<Model, S, EXACT>(a, i);
+  if (i < a.e.s.n) lane_one_sample_eval<Model, S, EXACT, FRAME>(a, i);
 }
 
 inline bool sample_eval_aligned(const SampleEvalArgs& a)
@@ -246,7 +305,7 @@ inline bool sample_eval_aligned(const SampleEvalArgs& a)
   return aligned16(s.ox) && aligned16(s.oy) && aligned16(s.oz) && aligned16(s.xi0) && aligned16(s.xi1) &&
          aligned16(s.dx) && aligned16(s.dy) && aligned16(s.dz) && aligned16(s.pdf) && aligned16(s.flag) &&
          aligned16(a.r) && aligned16(a.g) && aligned16(a.b) && aligned16(a.wr) && aligned16(a.wg) &&
-         aligned16(a.wb) && (reinterpret_cast<uintptr_t>(s.mask) & 3u) == 0;
+         aligned16(a.wb) && aligned16(a.nx) && aligned16(a.ny) && aligned16(a.nz) && (reinterpret_cast<uintptr_t>(s.mask) & 3u) == 0;
 }
 
 // What the exact mode launches for a row: the sampler's twin where it has one (launch_sample_mask), evaluated with
@@ -254,7 +313,7 @@ inline bool sample_eval_aligned(const SampleEvalArgs& a)
 template<class Model> constexpr bool sample_eval_has_exact() { return has_exact_sample<Model>() || model_has_exact<Model>(); }
 
 // One mode's launch: K the kernels' model type (the row's, or its sampler's exact twin), QUAD the mode's trait.
-template<class K, bool E, bool QUAD>
+template<class K, bool E, bool QUAD, bool FRAME>
 void launch_sample_eval_kernel(const SampleEvalArgs& a, hipStream_t s)
 {
   const bool vec = QUAD && sample_eval_aligned(a);
@@ -264,13 +323,13 @@ void launch_sample_eval_kernel(const SampleEvalArgs& a, hipStream_t s)
   if (blocks > max_blocks()) blocks = max_blocks();
   if constexpr (QUAD)
   {
-    if (vec) hipLaunchKernelGGL((k_sample_eval_v4<K, E>), dim3(unsigned(blocks)), dim3(kBlock), 0, s, a);
+    if (vec) hipLaunchKernelGGL((k_sample_eval_v4<K, E, FRAME>), dim3(unsigned(blocks)), dim3(kBlock), 0, s, a);
   }
-  if (!vec) hipLaunchKernelGGL((k_sample_eval_v1<K, E>), dim3(unsigned(blocks)), dim3(kBlock), 0, s, a);
+  if (!vec) hipLaunchKernelGGL((k_sample_eval_v1<K, E, FRAME>), dim3(unsigned(blocks)), dim3(kBlock), 0, s, a);
 }
 
-template<class Model>
-int launch_sample_eval(const SampleEvalArgs& a0, hipStream_t s)
+template<class Model, bool FRAME>
+int launch_sample_eval_frame(const SampleEvalArgs& a0, hipStream_t s)
 {
   if (const int rc = host_prepare<Model>::run(s)) return rc;
   if (const int rc = host_validate<Model>::run(a0.s.p)) return rc;
@@ -282,17 +341,22 @@ int launch_sample_eval(const SampleEvalArgs& a0, hipStream_t s)
   if constexpr (sample_eval_has_exact<Model>())
     if (exact_on())
     {
-      launch_sample_eval_kernel<exact_sample_t<Model>, model_has_exact<Model>(), sample_eval_quad<Model, true>::value>(a, s);
+      launch_sample_eval_kernel<exact_sample_t<Model>, model_has_exact<Model>(),
+                                sample_eval_use_quad<FRAME, Model, true>(), FRAME>(a, s);
       exact = true;
     }
-  if (!exact) launch_sample_eval_kernel<Model, false, sample_eval_quad<Model, false>::value>(a, s);
+  if (!exact) launch_sample_eval_kernel<Model, false, sample_eval_use_quad<FRAME, Model, false>(), FRAME>(a, s);
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) return fail(BBM_HIP_ERR_HIP, std::string("kernel launch failed: ") + hipGetErrorString(e));
   return BBM_HIP_OK;
 }
 
+// the local call, and the world-space one (a.nx / ny / nz set)
+template<class Model> int launch_sample_eval(const SampleEvalArgs& a, hipStream_t s) { return launch_sample_eval_frame<Model, false>(a, s); }
+template<class Model> int launch_sample_eval_world(const SampleEvalArgs& a, hipStream_t s) { return launch_sample_eval_frame<Model, true>(a, s); }
+
 // a full grid, as the other per-lane kernels; 0 where the batch is too large for one launch (var_blocks)
-template<class K, int S, bool E, bool QUAD>
+template<class K, int S, bool E, bool QUAD, bool FRAME>
 unsigned launch_sample_eval_tab_kernel(const SampleEvalTabArgs& a, hipStream_t s)
 {
   const bool vec = QUAD && sample_eval_aligned(a.e) && a.src.aligned(S);
@@ -300,16 +364,16 @@ unsigned launch_sample_eval_tab_kernel(const SampleEvalTabArgs& a, hipStream_t s
   if (blocks == 0) return blocks;
   if constexpr (QUAD)
   {
-    if (vec) hipLaunchKernelGGL((k_seval_lane4<K, S, E, SampleEvalTabArgs>), dim3(blocks), dim3(kBlock), 0, s, a);
+    if (vec) hipLaunchKernelGGL((k_seval_lane4<K, S, E, FRAME, SampleEvalTabArgs>), dim3(blocks), dim3(kBlock), 0, s, a);
   }
-  if (!vec) hipLaunchKernelGGL((k_seval_lane1<K, S, E, SampleEvalTabArgs>), dim3(blocks), dim3(kBlock), 0, s, a);
+  if (!vec) hipLaunchKernelGGL((k_seval_lane1<K, S, E, FRAME, SampleEvalTabArgs>), dim3(blocks), dim3(kBlock), 0, s, a);
   return blocks;
 }
 
 // The table's blocks were prepared at create (table_prepare: host_prepare, host_validate, host_params per material),
 // so, as for launch_sample_lanes, nothing is left to do on the host but choose the kernel.
-template<class Model>
-int launch_sample_eval_tab(const SampleEvalTabArgs& a, hipStream_t s)
+template<class Model, bool FRAME>
+int launch_sample_eval_tab_frame(const SampleEvalTabArgs& a, hipStream_t s)
 {
   if constexpr (!supports_varying<Model>::value) return var_unsupported();
   else
@@ -318,9 +382,13 @@ int launch_sample_eval_tab(const SampleEvalTabArgs& a, hipStream_t s)
     if constexpr (sample_eval_has_exact<Model>())
       if (exact_on())
         return var_launched(launch_sample_eval_tab_kernel<exact_sample_t<Model>, S, model_has_exact<Model>(),
-                                                          sample_eval_tab_quad<Model, true>::value>(a, s));
-    return var_launched(launch_sample_eval_tab_kernel<Model, S, false, sample_eval_tab_quad<Model, false>::value>(a, s));
+                                                          sample_eval_tab_use_quad<FRAME, Model, true>(), FRAME>(a, s));
+    return var_launched(launch_sample_eval_tab_kernel<Model, S, false, sample_eval_tab_use_quad<FRAME, Model, false>(),
+                                                      FRAME>(a, s));
   }
 }
+
+template<class Model> int launch_sample_eval_tab(const SampleEvalTabArgs& a, hipStream_t s) { return launch_sample_eval_tab_frame<Model, false>(a, s); }
+template<class Model> int launch_sample_eval_tab_world(const SampleEvalTabArgs& a, hipStream_t s) { return launch_sample_eval_tab_frame<Model, true>(a, s); }
 
 }  // namespace bbmhip

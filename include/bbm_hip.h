@@ -253,6 +253,53 @@ int bbm_hip_reflectance_table(const bbm_hip_table* table, int call_flags, const 
                               const uint8_t* mask, size_t n, uint32_t component, uint32_t unit,
                               float* r, float* g, float* b, void* stream);
 
+/* ---------------------------------------------------------------- world space: per-lane shading frames */
+
+/* Every batch call above takes and returns directions in the local shading frame (z is the normal).  These calls
+ * carry a batch between world space and the frame of one shading normal per lane: the reference's
+ * toGlobalShadingFrame(normal) (core/shading_frame.h:26-58, Duff et al.'s basis; the tangent follows from the normal),
+ * with the arithmetic bbm_hip_render_sphere uses for its pixels.  The normal may have any length, it is normalised
+ * inside.  Lane i of bbm_hip_frame_to_local writes transpose(M_i) v_i (toLocalShadingFrame), lane i of
+ * bbm_hip_frame_to_global writes M_i v_i.  A lane whose normal has |n|^2 <= epsilon(float) (or is NaN), and a lane
+ * with mask[i] == 0, writes (0, 0, 0).  n == 0 is a no-op; else mask may be NULL and every other pointer is required
+ * (BBM_HIP_ERR_INVALID_ARG before any launch).  The outputs may not overlap the inputs.  Arrays
+ * that are not all 16-byte aligned take the one-lane kernel.  floatRGB only. */
+int bbm_hip_frame_to_local(const float* nx, const float* ny, const float* nz,
+                           const float* x, const float* y, const float* z, const uint8_t* mask, size_t n,
+                           float* lx, float* ly, float* lz, void* stream);
+int bbm_hip_frame_to_global(const float* nx, const float* ny, const float* nz,
+                            const float* lx, const float* ly, const float* lz, const uint8_t* mask, size_t n,
+                            float* x, float* y, float* z, void* stream);
+
+/* bbm_hip_sample_eval / bbm_hip_sample_eval_table for a renderer's bounce: `out` and the returned dir are in world
+ * space, (nx, ny, nz) is the shading normal per lane, and the frame is built and applied in registers inside the
+ * kernel (64 B per lane with the weight alone, against 124 B and three launches for the staged calls).  Every other
+ * argument, the output groups, the modes and the errors are those of the local call; the normal pointers are
+ * required.  For lane i every output equals, bit for bit, what these three calls return in sequence with the same
+ * mask: bbm_hip_frame_to_local(normal, out), the local call on the result, bbm_hip_frame_to_global(normal, dir).
+ * So pdf, flag, value and weight are the local call's, and the weight's cosine is the local dir_z.  What that means
+ * lane by lane:
+ *   a lane with mask[i] == 0  runs the local call's masked lane (component 0) at out = (0, 0, 0); dir = (0, 0, 0);
+ *   a lane whose normal is not live (|n|^2 <= epsilon(float), NaN)  the same, whatever its mask: exactly the staged
+ *                             calls' outputs for that lane with mask[i] == 0;
+ *   a table lane with material[i] >= nmaterials  the local table call's masked lane at the transformed out, and its
+ *                             direction transformed to world space, as the staged calls do.
+ * All 49 rows; the table call for the rows bbm_hip_model_has_table reports. */
+int bbm_hip_sample_eval_world(int model_id, const float* params, int nparams,
+                              const float* nx, const float* ny, const float* nz,
+                              const float* out_x, const float* out_y, const float* out_z,
+                              const float* xi0, const float* xi1,
+                              const uint8_t* mask, size_t n, uint32_t component, uint32_t unit,
+                              float* dir_x, float* dir_y, float* dir_z, float* pdf, uint32_t* flag,
+                              float* r, float* g, float* b, float* wr, float* wg, float* wb, void* stream);
+int bbm_hip_sample_eval_table_world(const bbm_hip_table* table, int call_flags, const uint32_t* material,
+                                    const float* nx, const float* ny, const float* nz,
+                                    const float* out_x, const float* out_y, const float* out_z,
+                                    const float* xi0, const float* xi1,
+                                    const uint8_t* mask, size_t n, uint32_t component, uint32_t unit,
+                                    float* dir_x, float* dir_y, float* dir_z, float* pdf, uint32_t* flag,
+                                    float* r, float* g, float* b, float* wr, float* wg, float* wb, void* stream);
+
 /* ---------------------------------------------------------------- doubleRGB (Value = double) */
 
 /* The reference's doubleRGB configuration (backbone/native/include/backbone.h:41-42: Value = double, Spectrum =
