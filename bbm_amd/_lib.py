@@ -43,6 +43,7 @@ SIGNATURES = {
     "bbm_hip_sample": (_I, [_I, _P, _I, _P, _P, _P, _P, _P, _P, _SZ, _U32, _U32, _P, _P, _P, _P, _P, _P]),
     "bbm_hip_sample_eval": (_I, [_I, _P, _I, _P, _P, _P, _P, _P, _P, _SZ, _U32, _U32] + [_P] * 12),
     "bbm_hip_sample_eval_world": (_I, [_I, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _SZ, _U32, _U32] + [_P] * 12),
+    "bbm_hip_eval_pdf_world": (_I, [_I, _P, _I] + [_P] * 10 + [_SZ, _U32, _U32] + [_P] * 6),
     "bbm_hip_frame_to_local": (_I, [_P, _P, _P, _P, _P, _P, _P, _SZ, _P, _P, _P, _P]),
     "bbm_hip_frame_to_global": (_I, [_P, _P, _P, _P, _P, _P, _P, _SZ, _P, _P, _P, _P]),
     "bbm_hip_reflectance": (_I, [_I, _P, _I, _P, _P, _P, _P, _SZ, _U32, _U32, _P, _P, _P, _P]),
@@ -59,6 +60,7 @@ SIGNATURES = {
     "bbm_hip_sample_table": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _P, _SZ, _U32, _U32, _P, _P, _P, _P, _P, _P]),
     "bbm_hip_sample_eval_table": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _P, _SZ, _U32, _U32] + [_P] * 12),
     "bbm_hip_sample_eval_table_world": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _SZ, _U32, _U32] + [_P] * 12),
+    "bbm_hip_eval_pdf_table_world": (_I, [_P, _I, _P] + [_P] * 10 + [_SZ, _U32, _U32] + [_P] * 6),
     "bbm_hip_reflectance_table": (_I, [_P, _I, _P, _P, _P, _P, _P, _SZ, _U32, _U32, _P, _P, _P, _P]),
     "bbm_hip_model_has_f64": (_I, [_I]),
     "bbm_hip_eval_pdf_f64": (_I, [_I, _P, _I, _P, _P, _P, _P, _P, _P, _P, _SZ, _U32, _U32, _P, _P, _P, _P, _P]),

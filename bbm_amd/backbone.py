@@ -181,6 +181,27 @@ def _normal_rows(normal, like, what="normal"):
     return normal[0].data_ptr(), normal[1].data_ptr(), normal[2].data_ptr()
 
 
+def _world_normal(normal, cosine, varying, in_, out):
+    """The world-space keywords of eval_pdf, checked ahead of every other argument: the normals' row pointers, or None
+    for the local call.  cosine needs a normal; normal= excludes varying= and float64 directions."""
+    if normal is None:
+        if cosine:
+            raise ValueError("cosine=True needs normal=: the cosine is that of `in` against the shading normal")
+        return None
+    if varying is not None:
+        raise ValueError("normal= with varying=: there is no world-space call over per-lane parameters; "
+                         "take the directions through to_local(normal, .) and use the local call")
+    nptr = _normal_rows(normal, in_)
+    if _is_f64(in_) or _is_f64(out):
+        raise TypeError("normal: the world-space calls are floatRGB only (float32 directions)")
+    return nptr
+
+
+def _with_cosine(result, k, cosine):
+    """eval / pdf: element k of eval_pdf's result, and its cosine (the last element) where that was asked for."""
+    return (result[k], result[-1]) if cosine else result[k]
+
+
 def _frame_call(fn_name, normal, v, mask, stream):
     torch = _torch()
     nptr = _normal_rows(normal, v)
@@ -503,10 +524,16 @@ class BsdfModel:
         return rgb, pdf
 
     def eval_pdf(self, in_, out, component=bsdf_flag.All, unit=unit_t.Radiance, mask=None, *,
-                 rgb=None, pdf=None, stream=None, mode=3, params64=None, exact=None, varying=None):
+                 rgb=None, pdf=None, stream=None, mode=3, params64=None, exact=None, varying=None, normal=None,
+                 cosine=False):
         """varying: per-lane parameters, {attribute name or parameter index: float32 CUDA rows} (_varying); lane i
-        then evaluates the model with those parameters replaced by row[i] (bbm_hip_eval_pdf_varying)."""
+        then evaluates the model with those parameters replaced by row[i] (bbm_hip_eval_pdf_varying).
+        normal: a (3, N) float32 tensor of shading normals selects the world-space call (bbm_hip_eval_pdf_world):
+        `in_` and `out` are in world space, and the result is what to_local(normal, in_), to_local(normal, out) and
+        this call give in sequence, in one launch.  cosine=True (with normal=): the result gains a last element, the
+        (N,) cosine of `in_` against the normal (the z of to_local(normal, in_)).  floatRGB only, not with varying=."""
         torch = _torch()
+        nptr = _world_normal(normal, cosine, varying, in_, out)
         if varying is not None and _is_f64(in_):
             raise TypeError("varying: per-lane parameters are floatRGB only (float32 tensors)")
         if _is_f64(in_):
@@ -522,6 +549,13 @@ class BsdfModel:
         s = _stream_ptr(stream)
         _on_stream(stream, _keep, rgb, pdf)
         mid = self._call_id(exact)
+        if nptr is not None:
+            cos = torch.empty((n,), dtype=torch.float32, device=dev) if cosine else None
+            _on_stream(stream, cos)
+            _lib.check(lib.bbm_hip_eval_pdf_world(
+                mid, self._pptr(), self._params.size, *nptr, ix, iy, iz, ox, oy, oz, mptr, n, int(component), int(unit),
+                *_eval_pdf_ptrs(mode, rgb, pdf), None if cos is None else cos.data_ptr(), s))
+            return (rgb, pdf, cos) if cosine else (rgb, pdf)
         if varying is not None:
             vptr, vrows = self._varying(varying, n, _device(in_))
             _on_stream(stream, *vrows)
@@ -543,12 +577,14 @@ class BsdfModel:
         return rgb, pdf
 
     def eval(self, in_, out, component=bsdf_flag.All, unit=unit_t.Radiance, mask=None, **kw):
-        """Spectrum eval(in, out, component, unit, mask) for N pairs -> (3, N) RGB."""
-        return self.eval_pdf(in_, out, component, unit, mask, mode=1, **kw)[0]
+        """Spectrum eval(in, out, component, unit, mask) for N pairs -> (3, N) RGB; with normal= and cosine=True
+        (eval_pdf) -> (RGB, cosine)."""
+        return _with_cosine(self.eval_pdf(in_, out, component, unit, mask, mode=1, **kw), 0, kw.get("cosine", False))
 
     def pdf(self, in_, out, component=bsdf_flag.All, unit=unit_t.Radiance, mask=None, **kw):
-        """Value pdf(in, out, component, unit, mask) for N pairs -> (N,)."""
-        return self.eval_pdf(in_, out, component, unit, mask, mode=2, **kw)[1]
+        """Value pdf(in, out, component, unit, mask) for N pairs -> (N,); with normal= and cosine=True (eval_pdf)
+        -> (pdf, cosine)."""
+        return _with_cosine(self.eval_pdf(in_, out, component, unit, mask, mode=2, **kw), 1, kw.get("cosine", False))
 
     def sample(self, out, xi, component=bsdf_flag.All, unit=unit_t.Radiance, mask=None, *, stream=None,
                params64=None, exact=None, varying=None):
@@ -883,7 +919,14 @@ class AggregateModel:
         return False
 
     def eval_pdf(self, in_, out, component=bsdf_flag.All, unit=unit_t.Radiance, mask=None, *,
-                 rgb=None, pdf=None, stream=None, mode=3, varying=None):
+                 rgb=None, pdf=None, stream=None, mode=3, varying=None, normal=None, cosine=False):
+        """normal, cosine: BsdfModel.eval_pdf's, staged -- a tree has no fused kernel, so the directions go through
+        to_local(normal, .) and the cosine is the z of to_local(normal, in_)."""
+        if _world_normal(normal, cosine, varying, in_, out) is not None:
+            li = to_local(normal, in_, mask, stream=stream)
+            r = self.eval_pdf(li, to_local(normal, out, mask, stream=stream), component, unit, mask, rgb=rgb, pdf=pdf,
+                              stream=stream, mode=mode)
+            return (*r, li[2]) if cosine else r
         self._no_varying(varying)
         torch = _torch()
         f64 = _is_f64(in_)
@@ -1108,7 +1151,9 @@ class MaterialTable:
         return material.data_ptr()
 
     def eval_pdf(self, in_, out, component=bsdf_flag.All, unit=unit_t.Radiance, mask=None, *, material,
-                 rgb=None, pdf=None, stream=None, mode=3, exact=None):
+                 rgb=None, pdf=None, stream=None, mode=3, exact=None, normal=None, cosine=False):
+        """normal, cosine: as BsdfModel.eval_pdf's (bbm_hip_eval_pdf_table_world)."""
+        nptr = _world_normal(normal, cosine, None, in_, out)
         if _is_f64(in_) or _is_f64(out):
             raise TypeError("MaterialTable: material tables are floatRGB only (float32 tensors)")
         h = self._live()
@@ -1119,16 +1164,23 @@ class MaterialTable:
         mptr, _keep = _mask_ptr(mask, n)
         rgb, pdf = _eval_pdf_outputs(mode, n, dev, rgb, pdf)
         _on_stream(stream, _keep, rgb, pdf, material)
+        if nptr is not None:
+            cos = _torch().empty((n,), dtype=_torch().float32, device=dev) if cosine else None
+            _on_stream(stream, cos)
+            _lib.check(_lib.load().bbm_hip_eval_pdf_table_world(
+                h, self._flags(exact), idx, *nptr, ix, iy, iz, ox, oy, oz, mptr, n, int(component), int(unit),
+                *_eval_pdf_ptrs(mode, rgb, pdf), None if cos is None else cos.data_ptr(), _stream_ptr(stream)))
+            return (rgb, pdf, cos) if cosine else (rgb, pdf)
         _lib.check(_lib.load().bbm_hip_eval_pdf_table(
             h, self._flags(exact), idx, ix, iy, iz, ox, oy, oz, mptr, n, int(component), int(unit),
             *_eval_pdf_ptrs(mode, rgb, pdf), _stream_ptr(stream)))
         return rgb, pdf
 
     def eval(self, in_, out, component=bsdf_flag.All, unit=unit_t.Radiance, mask=None, **kw):
-        return self.eval_pdf(in_, out, component, unit, mask, mode=1, **kw)[0]
+        return _with_cosine(self.eval_pdf(in_, out, component, unit, mask, mode=1, **kw), 0, kw.get("cosine", False))
 
     def pdf(self, in_, out, component=bsdf_flag.All, unit=unit_t.Radiance, mask=None, **kw):
-        return self.eval_pdf(in_, out, component, unit, mask, mode=2, **kw)[1]
+        return _with_cosine(self.eval_pdf(in_, out, component, unit, mask, mode=2, **kw), 1, kw.get("cosine", False))
 
     def sample(self, out, xi, component=bsdf_flag.All, unit=unit_t.Radiance, mask=None, *, material, stream=None,
                exact=None):

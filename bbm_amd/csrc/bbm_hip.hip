@@ -431,6 +431,31 @@ int bbm_hip_sample_eval_world(int model_id, const float* params, int nparams,
                             mask, n, component, dir_x, dir_y, dir_z, pdf, flag, r, g, b, wr, wg, wb, stream);
 }
 
+// eval / pdf / eval + pdf in world space (eval_world.hpp).  The mode is taken from the outputs that are not NULL, with
+// bbm_hip_eval_pdf_varying's checks (eval_args); the normal is required, the cosine optional.
+int bbm_hip_eval_pdf_world(int model_id, const float* params, int nparams,
+                           const float* nx, const float* ny, const float* nz,
+                           const float* in_x, const float* in_y, const float* in_z,
+                           const float* out_x, const float* out_y, const float* out_z,
+                           const uint8_t* mask, size_t n, uint32_t component, uint32_t unit,
+                           float* r, float* g, float* b, float* pdf, float* cos_in, void* stream)
+{
+  (void)unit;
+  const CallExactScope mode_scope(model_id);
+  EvalArgs tmp;
+  const ModelEntry* e;
+  int rc = prepare(model_id, params, nparams, n, tmp, e);
+  if (rc) return rc;
+  if (n == 0) return BBM_HIP_OK;
+  if ((rc = check_dirs(nx, ny, nz, "normal"))) return rc;
+  EvalWorldArgs a;
+  int mode = 0;
+  if ((rc = eval_args(mode, in_x, in_y, in_z, out_x, out_y, out_z, mask, n, component, r, g, b, pdf, a.e))) return rc;
+  a.e.p = tmp.p;
+  a.nx = nx; a.ny = ny; a.nz = nz; a.cos = cos_in;
+  return e->run.eval_pdf_world(a, mode, static_cast<hipStream_t>(stream));
+}
+
 // ------------------------------------------------------------------------------- shading frames (frame.hpp)
 
 static int frame_common(bool to_local, const float* nx, const float* ny, const float* nz,
@@ -686,6 +711,31 @@ int bbm_hip_eval_pdf_table(const bbm_hip_table* t, int call_flags, const uint32_
   a.e.p = (mode & kModePdf) ? t->first_prepared : t->first_raw;
   a.src = {(mode & kModePdf) ? t->prepared : t->raw, material, t->count};
   return t->e->run.eval_pdf_tab(a, mode, static_cast<hipStream_t>(stream));
+}
+
+int bbm_hip_eval_pdf_table_world(const bbm_hip_table* t, int call_flags, const uint32_t* material,
+                                 const float* nx, const float* ny, const float* nz,
+                                 const float* in_x, const float* in_y, const float* in_z,
+                                 const float* out_x, const float* out_y, const float* out_z,
+                                 const uint8_t* mask, size_t n, uint32_t component, uint32_t unit,
+                                 float* r, float* g, float* b, float* pdf, float* cos_in, void* stream)
+{
+  (void)unit;
+  int rc = table_call(t, call_flags, n, material);
+  if (rc) return rc;
+  if (!t->e->run.eval_pdf_tab_world)
+    return fail(BBM_HIP_ERR_UNSUPPORTED, std::string(t->e->name) + ": no material-table kernels");
+  if (n == 0) return BBM_HIP_OK;
+  if ((rc = check_dirs(nx, ny, nz, "normal"))) return rc;
+  const CallExactScope mode_scope(call_flags);
+  EvalTabWorldArgs a;
+  int mode = 0;
+  if ((rc = eval_args(mode, in_x, in_y, in_z, out_x, out_y, out_z, mask, n, component, r, g, b, pdf, a.e.e))) return rc;
+  // the block form the local call reads (bbm_hip_eval_pdf_table)
+  a.e.e.p = (mode & kModePdf) ? t->first_prepared : t->first_raw;
+  a.e.nx = nx; a.e.ny = ny; a.e.nz = nz; a.e.cos = cos_in;
+  a.src = {(mode & kModePdf) ? t->prepared : t->raw, material, t->count};
+  return t->e->run.eval_pdf_tab_world(a, mode, static_cast<hipStream_t>(stream));
 }
 
 int bbm_hip_sample_table(const bbm_hip_table* t, int call_flags, const uint32_t* material,

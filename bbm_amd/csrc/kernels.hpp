@@ -16,10 +16,12 @@
 #include <cstdint>
 #include <cstdlib>
 #include <string>
+#include <type_traits>
 
 #include "../../include/bbm_hip.h"
 #include "host.hpp"
 #include "math.hpp"
+#include "frame.hpp"
 #include "microfacet.hpp"
 #include "fit.hpp"
 
@@ -116,6 +118,47 @@ __device__ __forceinline__ void one_pair(const Model& m, const EvalArgs& a, uint
   model_eval_pdf<MODE, EXACT>(m, in, out, active ? a.component : 0u, rgb, pdf);
   if (MODE & kModeEval) { a.r[i] = rgb[0]; a.g[i] = rgb[1]; a.b[i] = rgb[2]; }
   if (MODE & kModePdf) a.pdf[i] = pdf;
+}
+
+// The world-space eval calls (bbm_hip_eval_pdf_world and its table twin; eval_world.hpp): `in` and
+// `out` in world space, one shading normal per lane and an optional cosine output.  A wrapper: EvalArgs is what the
+// local kernels take and stays as it is.
+struct EvalWorldArgs
+{
+  EvalArgs e;
+  const float* nx; const float* ny; const float* nz;   // the shading normal per lane, any length
+  float* cos;                                          // z of the local `in`; null: not stored
+};
+__host__ __device__ __forceinline__ const EvalArgs& eval_args_of(const EvalArgs& a) { return a; }
+__host__ __device__ __forceinline__ const EvalArgs& eval_args_of(const EvalWorldArgs& a) { return a.e; }
+
+// A world-space pair taken into the shading frame of its normal (frame.hpp), as two bbm_hip_frame_to_local calls
+// return it: +0 where the lane is masked (`on` false) or its normal is not live.  Returns whether it is neither;
+// the model then runs on (in, out) with the component cleared where it is not, which is the local call's masked lane
+// at in = out = 0.  in.z is the call's cosine.  The frame's nine floats are dead once this returns.
+__device__ __forceinline__ bool frame_pair(v3 normal, bool on, v3& in, v3& out)
+{
+  const Frame f = shading_frame(normal);
+  const bool in_frame = on && f.live;
+  const v3 li = f.to_local(in), lo = f.to_local(out);
+  in = in_frame ? li : mk3(0.0f, 0.0f, 0.0f);
+  out = in_frame ? lo : mk3(0.0f, 0.0f, 0.0f);
+  return in_frame;
+}
+
+// `on`: the lane's mask; `src_live`: a table lane's material index in range (it switches the component alone, as in
+// the local table call), true for the uniform call
+template<class Model, int MODE, bool EXACT = false>
+__device__ __forceinline__ void one_pair_world(const Model& m, const EvalWorldArgs& w, uint64_t i, bool on, bool src_live)
+{
+  const EvalArgs& a = w.e;
+  float rgb[3], pdf;
+  v3 in = mk3(a.ix[i], a.iy[i], a.iz[i]), out = mk3(a.ox[i], a.oy[i], a.oz[i]);
+  const bool in_frame = frame_pair(mk3(w.nx[i], w.ny[i], w.nz[i]), on, in, out);
+  model_eval_pdf<MODE, EXACT>(m, in, out, (in_frame && src_live) ? a.component : 0u, rgb, pdf);
+  if (MODE & kModeEval) { a.r[i] = rgb[0]; a.g[i] = rgb[1]; a.b[i] = rgb[2]; }
+  if (MODE & kModePdf) a.pdf[i] = pdf;
+  if (w.cos) w.cos[i] = in.z;
 }
 
 // Vector path: 4 consecutive pairs per thread-iteration, 16-byte loads/stores per array.
@@ -405,10 +448,17 @@ __device__ __forceinline__ void erfc_block(const Model& m, bool mine, v3 in, v3 
   ef.v[3] = dup3 ? ef.v[1] : ef.v[3];
 }
 
-template<class Model, int MODE, bool MASK>
-__global__ __launch_bounds__(kBlock) BBM_HIP_COMPACT_ATTR void k_eval_pdf_compact(EvalArgs a)
+//
+// FRAME: the world-space call (EvalWorldArgs).  The frame is applied in the load stage, so the
+// liveness test is made on the local directions and only those go to LDS; a masked pair or one whose normal is not
+// live is dead.  The owner thread stores the cosine there too, so it is not held across the evaluation.  The mask is
+// then a runtime, wave-uniform choice (MASK is not looked at).  Without FRAME the kernel holds nothing of this.
+template<class Model, int MODE, bool MASK, bool FRAME = false>
+__global__ __launch_bounds__(kBlock) BBM_HIP_COMPACT_ATTR
+void k_eval_pdf_compact(std::conditional_t<FRAME, EvalWorldArgs, EvalArgs> w)
 {
   math_tables_init();
+  const EvalArgs& a = eval_args_of(w);
   constexpr int kTile = 4 * kBlock;
   __shared__ float job[6][kTile];      // live pairs' in.xyz, out.xyz; rows 0..3 then hold rgb, pdf
   __shared__ int wave_total[kBlock / 64];
@@ -431,10 +481,27 @@ __global__ __launch_bounds__(kBlock) BBM_HIP_COMPACT_ATTR void k_eval_pdf_compac
     {
       ix = ld4<true>(a.ix, t); iy = ld4<true>(a.iy, t); iz = ld4<true>(a.iz, t);
       ox = ld4<true>(a.ox, t); oy = ld4<true>(a.oy, t); oz = ld4<true>(a.oz, t);
-      mk = MASK ? reinterpret_cast<const uint32_t*>(a.mask)[t] : 0x01010101u;
+      if constexpr (FRAME) mk = a.mask ? reinterpret_cast<const uint32_t*>(a.mask)[t] : 0x01010101u;
+      else mk = MASK ? reinterpret_cast<const uint32_t*>(a.mask)[t] : 0x01010101u;
     }
-    const float inx[4] = {ix.x, ix.y, ix.z, ix.w}, iny[4] = {iy.x, iy.y, iy.z, iy.w}, inz[4] = {iz.x, iz.y, iz.z, iz.w};
-    const float onx[4] = {ox.x, ox.y, ox.z, ox.w}, ony[4] = {oy.x, oy.y, oy.z, oy.w}, onz[4] = {oz.x, oz.y, oz.z, oz.w};
+    float inx[4] = {ix.x, ix.y, ix.z, ix.w}, iny[4] = {iy.x, iy.y, iy.z, iy.w}, inz[4] = {iz.x, iz.y, iz.z, iz.w};
+    float onx[4] = {ox.x, ox.y, ox.z, ox.w}, ony[4] = {oy.x, oy.y, oy.z, oy.w}, onz[4] = {oz.x, oz.y, oz.z, oz.w};
+    if constexpr (FRAME)
+    {
+      // into the lanes' shading frames (a thread without a quad has mk = 0: zeros); the cosine goes out here
+      float4 wx{}, wy{}, wz{};
+      if (have) { wx = ld4<true>(w.nx, t); wy = ld4<true>(w.ny, t); wz = ld4<true>(w.nz, t); }
+      const float nnx[4] = {wx.x, wx.y, wx.z, wx.w}, nny[4] = {wy.x, wy.y, wy.z, wy.w}, nnz[4] = {wz.x, wz.y, wz.z, wz.w};
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+      {
+        v3 in = mk3(inx[j], iny[j], inz[j]), out = mk3(onx[j], ony[j], onz[j]);
+        frame_pair(mk3(nnx[j], nny[j], nnz[j]), ((mk >> (8 * j)) & 0xffu) != 0, in, out);
+        inx[j] = in.x; iny[j] = in.y; inz[j] = in.z;
+        onx[j] = out.x; ony[j] = out.y; onz[j] = out.z;
+      }
+      if (have && w.cos) st4<true>(w.cos, t, inz[0], inz[1], inz[2], inz[3]);
+    }
     bool live[4];
     int cnt = 0;
 #pragma unroll
@@ -569,7 +636,8 @@ __global__ __launch_bounds__(kBlock) BBM_HIP_COMPACT_ATTR void k_eval_pdf_compac
   if (blockIdx.x == 0 && threadIdx.x < (a.n & 3))
   {
     const uint64_t i = (n4 << 2) + threadIdx.x;
-    one_pair<Model, MODE>(m, a, i, MASK ? (a.mask[i] != 0) : true);
+    if constexpr (FRAME) one_pair_world<Model, MODE>(m, w, i, a.mask ? (a.mask[i] != 0) : true, true);
+    else one_pair<Model, MODE>(m, a, i, MASK ? (a.mask[i] != 0) : true);
   }
 }
 
@@ -1155,6 +1223,7 @@ int launch_loss(const LossArgs& a0, hipStream_t s)
 #include "table.hpp"
 #include "lanes.hpp"
 #include "sample_eval.hpp"
+#include "eval_world.hpp"
 
 namespace bbmhip {
 
@@ -1173,6 +1242,8 @@ using SampleTabLauncher = int (*)(const SampleTabArgs&, hipStream_t);
 using ReflTabLauncher = int (*)(const ReflTabArgs&, hipStream_t);
 using SampleEvalLauncher = int (*)(const SampleEvalArgs&, hipStream_t);
 using SampleEvalTabLauncher = int (*)(const SampleEvalTabArgs&, hipStream_t);
+using EvalWorldLauncher = int (*)(const EvalWorldArgs&, int, hipStream_t);
+using EvalTabWorldLauncher = int (*)(const EvalTabWorldArgs&, int, hipStream_t);
 
 // A composition's launchers: what a registry row (registry.hip) holds of its kernels.
 struct Launchers
@@ -1198,6 +1269,9 @@ struct Launchers
   // the same in world space: per-lane shading frames inside the kernel (sample_eval.hpp, FRAME)
   SampleEvalLauncher sample_eval_world;
   SampleEvalTabLauncher sample_eval_tab_world;
+  // eval / pdf / eval + pdf in world space (eval_world.hpp); the table twin null where there are no tables
+  EvalWorldLauncher eval_pdf_world;
+  EvalTabWorldLauncher eval_pdf_tab_world;
 };
 template<class M> constexpr Launchers launchers()
 {
@@ -1208,11 +1282,11 @@ template<class M> constexpr Launchers launchers()
             &table_prepare<M>, &launch_eval_pdf_lanes<M, EvalTabArgs>, &launch_sample_lanes<M, SampleTabArgs>,
             &launch_reflectance_lanes<M, ReflTabArgs>,
             &launch_sample_eval<M>, &launch_sample_eval_tab<M>, &launch_sample_eval_world<M>,
-            &launch_sample_eval_tab_world<M>};
+            &launch_sample_eval_tab_world<M>, &launch_eval_pdf_world<M>, &launch_eval_pdf_tab_world<M>};
   else
     return {&launch_eval_pdf<M>, &launch_sample<M>, &launch_reflectance<M>, &launch_loss<M>, &launch_check<M>, &launch_image<M>,
             nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &launch_sample_eval<M>, nullptr,
-            &launch_sample_eval_world<M>, nullptr};
+            &launch_sample_eval_world<M>, nullptr, &launch_eval_pdf_world<M>, nullptr};
 }
 
 }  // namespace bbmhip

@@ -31,7 +31,7 @@
 
 namespace bbmhip {
 
-template<class Args, class S> struct LaneArgs { using Src = S; Args e; S src; };
+template<class Args, class S> struct LaneArgs { using Src = S; using Call = Args; Args e; S src; };
 
 // named, so that a kernel's symbol carries a short name and not the template's
 struct EvalVarArgs : LaneArgs<EvalArgs, VarRows> {};
@@ -40,43 +40,71 @@ struct ReflVarArgs : LaneArgs<ReflArgs, VarRows> {};
 struct EvalTabArgs : LaneArgs<EvalArgs, TabRef> {};      // e.p: the fallback block (and the aggregate mode slot)
 struct SampleTabArgs : LaneArgs<SampleArgs, TabRef> {};
 struct ReflTabArgs : LaneArgs<ReflArgs, TabRef> {};
+// The world-space table call (bbm_hip_eval_pdf_table_world): the eval kernels below over
+// EvalWorldArgs.  The frame is a property of the argument type (lane_frame), so the local instantiations keep their
+// names and hold nothing of it.  Instantiated for TabRef only: there is no world-space call over rows.
+struct EvalTabWorldArgs : LaneArgs<EvalWorldArgs, TabRef> {};
+template<class A> constexpr bool lane_frame = std::is_same_v<typename A::Call, EvalWorldArgs>;
 
 template<class Model, int MODE, bool EXACT, class A>
 __device__ __forceinline__ void lane_one_pair(const A& a, uint64_t i)
 {
   constexpr int S = A::Src::template slots<Model>;
-  const EvalArgs& e = a.e;
+  const EvalArgs& e = eval_args_of(a.e);
   const auto l = a.src.load_lane(i);
   ParamBlock q;
   a.src.template lane_block<S>(e.p, l, i, q);
   const Model m(q.v);
-  float rgb[3], pdf;
-  bool active = e.mask ? (e.mask[i] != 0) : true;
-  active = active && a.src.lane_live(l);
-  model_eval_pdf<MODE, EXACT>(m, mk3(e.ix[i], e.iy[i], e.iz[i]), mk3(e.ox[i], e.oy[i], e.oz[i]),
-                              active ? e.component : 0u, rgb, pdf);
-  if (MODE & kModeEval) { e.r[i] = rgb[0]; e.g[i] = rgb[1]; e.b[i] = rgb[2]; }
-  if (MODE & kModePdf) e.pdf[i] = pdf;
+  if constexpr (lane_frame<A>) one_pair_world<Model, MODE, EXACT>(m, a.e, i, e.mask ? (e.mask[i] != 0) : true, a.src.lane_live(l));
+  else
+  {
+    float rgb[3], pdf;
+    bool active = e.mask ? (e.mask[i] != 0) : true;
+    active = active && a.src.lane_live(l);
+    model_eval_pdf<MODE, EXACT>(m, mk3(e.ix[i], e.iy[i], e.iz[i]), mk3(e.ox[i], e.oy[i], e.oz[i]),
+                                active ? e.component : 0u, rgb, pdf);
+    if (MODE & kModeEval) { e.r[i] = rgb[0]; e.g[i] = rgb[1]; e.b[i] = rgb[2]; }
+    if (MODE & kModePdf) e.pdf[i] = pdf;
+  }
 }
 
 // Four pairs per thread; every float array and the source's own 16-byte aligned, the mask 4-byte aligned.
+// lane_frame<A>: three more loads (the normal), the pair taken into its frame before the model is built, and one
+// more store where the cosine is asked for (runtime, wave-uniform).
 template<class Model, int MODE, bool EXACT, class A>
 __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(eval_waves<Model>::value, 8)))
 void k_eval_lane4(A a)
 {
   math_tables_init();
   constexpr int S = A::Src::template slots<Model>;
-  const EvalArgs& e = a.e;
+  const EvalArgs& e = eval_args_of(a.e);
   const uint64_t n4 = e.n >> 2;
   const uint64_t t = uint64_t(blockIdx.x) * kBlock + threadIdx.x;
   if (t < n4)
   {
     const float4 ix = ld4<true>(e.ix, t), iy = ld4<true>(e.iy, t), iz = ld4<true>(e.iz, t);
     const float4 ox = ld4<true>(e.ox, t), oy = ld4<true>(e.oy, t), oz = ld4<true>(e.oz, t);
+    float4 wx = {}, wy = {}, wz = {};
+    if constexpr (lane_frame<A>) { wx = ld4<true>(a.e.nx, t); wy = ld4<true>(a.e.ny, t); wz = ld4<true>(a.e.nz, t); }
     const auto c = a.src.template load_quad<S>(t);
     const uint32_t mk = e.mask ? reinterpret_cast<const uint32_t*>(e.mask)[t] : 0x01010101u;
-    const float inx[4] = {ix.x, ix.y, ix.z, ix.w}, iny[4] = {iy.x, iy.y, iy.z, iy.w}, inz[4] = {iz.x, iz.y, iz.z, iz.w};
-    const float onx[4] = {ox.x, ox.y, ox.z, ox.w}, ony[4] = {oy.x, oy.y, oy.z, oy.w}, onz[4] = {oz.x, oz.y, oz.z, oz.w};
+    float inx[4] = {ix.x, ix.y, ix.z, ix.w}, iny[4] = {iy.x, iy.y, iy.z, iy.w}, inz[4] = {iz.x, iz.y, iz.z, iz.w};
+    float onx[4] = {ox.x, ox.y, ox.z, ox.w}, ony[4] = {oy.x, oy.y, oy.z, oy.w}, onz[4] = {oz.x, oz.y, oz.z, oz.w};
+    bool in_frame[4] = {true, true, true, true};
+    if constexpr (lane_frame<A>)
+    {
+      // every pair into its frame first (frame_pair): the frames are dead before the first model is built
+      const float nnx[4] = {wx.x, wx.y, wx.z, wx.w}, nny[4] = {wy.x, wy.y, wy.z, wy.w}, nnz[4] = {wz.x, wz.y, wz.z, wz.w};
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+      {
+        v3 in = mk3(inx[j], iny[j], inz[j]), out = mk3(onx[j], ony[j], onz[j]);
+        in_frame[j] = frame_pair(mk3(nnx[j], nny[j], nnz[j]), ((mk >> (8 * j)) & 0xffu) != 0, in, out);
+        inx[j] = in.x; iny[j] = in.y; inz[j] = in.z;
+        onx[j] = out.x; ony[j] = out.y; onz[j] = out.z;
+      }
+      if (a.e.cos) st4<true>(a.e.cos, t, inz[0], inz[1], inz[2], inz[3]);
+    }
     float r[4], g[4], b[4], p[4];
 #pragma unroll
     for (int j = 0; j < 4; ++j)
@@ -86,6 +114,7 @@ void k_eval_lane4(A a)
       const Model m(q.v);
       float rgb[3];
       bool active = (mk >> (8 * j)) & 0xffu;
+      if constexpr (lane_frame<A>) active = in_frame[j];
       active = active && a.src.quad_live(c, j);
       const uint32_t comp = active ? e.component : 0u;
       model_eval_pdf<MODE, EXACT>(m, mk3(inx[j], iny[j], inz[j]), mk3(onx[j], ony[j], onz[j]), comp, rgb, p[j]);
@@ -162,7 +191,7 @@ void k_eval_lane1(A a)
 {
   math_tables_init();
   const uint64_t i = uint64_t(blockIdx.x) * kBlock + threadIdx.x;
-  if (i < a.e.n) lane_one_pair<Model, MODE, EXACT>(a, i);
+  if (i < eval_args_of(a.e).n) lane_one_pair<Model, MODE, EXACT>(a, i);
 }
 
 template<class Model, int S, class A>
@@ -232,18 +261,28 @@ struct LaneHost
   ~LaneHost() { host_params<Model>::done(scratch, s); }
 };
 
+// Whether the quad form is used for aligned arrays: the source's choice, and for the world-space table call its own
+// on top of that (eval_tab_world_quad, judged per mode from the resource report; models.hpp).
+template<class Model, int MODE, bool EXACT> struct eval_tab_world_quad { static constexpr bool value = true; };
+template<class Model, int MODE, bool EXACT, class A> constexpr bool lane_quad()
+{
+  if constexpr (lane_frame<A>) return A::Src::template quad<Model> && eval_tab_world_quad<Model, MODE, EXACT>::value;
+  else return A::Src::template quad<Model>;
+}
+
 // The ladder: alignment -> the quad or the one-lane kernel.
 template<class Model, int MODE, bool EXACT, class A>
 int launch_lane_kernel(const A& a, hipStream_t s)
 {
   using Src = typename A::Src;
-  constexpr bool quad = Src::template quad<Model>;
-  const EvalArgs& e = a.e;
+  constexpr bool quad = lane_quad<Model, MODE, EXACT, A>();
+  const EvalArgs& e = eval_args_of(a.e);
   bool vec = quad && aligned16(e.ix) && aligned16(e.iy) && aligned16(e.iz) && aligned16(e.ox) && aligned16(e.oy) &&
              aligned16(e.oz) && (reinterpret_cast<uintptr_t>(e.mask) & 3u) == 0 &&
              a.src.aligned(Src::template slots<Model>);
   if (MODE & kModeEval) vec = vec && aligned16(e.r) && aligned16(e.g) && aligned16(e.b);
   if (MODE & kModePdf) vec = vec && aligned16(e.pdf);
+  if constexpr (lane_frame<A>) vec = vec && aligned16(a.e.nx) && aligned16(a.e.ny) && aligned16(a.e.nz) && aligned16(a.e.cos);
   const unsigned blocks = var_blocks(vec ? (e.n >> 2) : e.n);
   if (blocks == 0) return var_launched(blocks);
   if constexpr (quad)

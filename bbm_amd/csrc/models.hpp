@@ -235,6 +235,15 @@ BBM_HIP_WORLD_ONE_LANE_T(AggNganASM)
 BBM_HIP_WORLD_ONE_LANE_T(AggPhongM)
 BBM_HIP_WORLD_ONE_LANE_T(AggNganLafortuneM)
 
+
+// eval_pdf in world space (eval_world.hpp, lanes.hpp over EvalTabWorldArgs), judged the same way.
+// The frame is dead before the model runs, so no quad kernel gains scratch or AGPRs over its local form but the
+// compact rows' eval + pdf quad (262-266 VGPRs + 6-10 AGPRs at one wave, the one-lane kernel 161-183 and none at two
+// or three) -- a kernel the library launches only with compaction switched off (an experimental build); those rows
+// have no world quad at all.  The table kernels need nothing: EPD's 8 B are in its one-lane kernel too.
+template<class M, int MODE, bool EXACT> requires compact_eval<M>::value
+struct eval_world_quad<M, MODE, EXACT> { static constexpr bool value = false; };
+
 }  // namespace bbmhip
 
 // X(composition) per instantiation unit
@@ -270,7 +279,9 @@ BBM_HIP_WORLD_ONE_LANE_T(AggNganLafortuneM)
   template int launch_sample_eval<M>(const SampleEvalArgs&, hipStream_t);     \
   template int launch_sample_eval_tab<M>(const SampleEvalTabArgs&, hipStream_t); \
   template int launch_sample_eval_world<M>(const SampleEvalArgs&, hipStream_t); \
-  template int launch_sample_eval_tab_world<M>(const SampleEvalTabArgs&, hipStream_t);
+  template int launch_sample_eval_tab_world<M>(const SampleEvalTabArgs&, hipStream_t); \
+  template int launch_eval_pdf_world<M>(const EvalWorldArgs&, int, hipStream_t); \
+  template int launch_eval_pdf_tab_world<M>(const EvalTabWorldArgs&, int, hipStream_t);
 #define BBM_HIP_EXTERN(M)                                                       \
   extern template int launch_eval_pdf<M>(const EvalArgs&, int, hipStream_t);    \
   extern template int launch_sample<M>(const SampleArgs&, hipStream_t);         \
@@ -288,4 +299,6 @@ BBM_HIP_WORLD_ONE_LANE_T(AggNganLafortuneM)
   extern template int launch_sample_eval<M>(const SampleEvalArgs&, hipStream_t); \
   extern template int launch_sample_eval_tab<M>(const SampleEvalTabArgs&, hipStream_t); \
   extern template int launch_sample_eval_world<M>(const SampleEvalArgs&, hipStream_t); \
-  extern template int launch_sample_eval_tab_world<M>(const SampleEvalTabArgs&, hipStream_t);
+  extern template int launch_sample_eval_tab_world<M>(const SampleEvalTabArgs&, hipStream_t); \
+  extern template int launch_eval_pdf_world<M>(const EvalWorldArgs&, int, hipStream_t); \
+  extern template int launch_eval_pdf_tab_world<M>(const EvalTabWorldArgs&, int, hipStream_t);

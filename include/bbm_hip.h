@@ -300,6 +300,37 @@ int bbm_hip_sample_eval_table_world(const bbm_hip_table* table, int call_flags, 
                                     float* dir_x, float* dir_y, float* dir_z, float* pdf, uint32_t* flag,
                                     float* r, float* g, float* b, float* wr, float* wg, float* wb, void* stream);
 
+/* bbm_hip_eval_pdf / bbm_hip_eval_pdf_table for a renderer's next-event estimation: `in` (towards the light) and
+ * `out` are in world space, (nx, ny, nz) is the shading normal per lane, and the frame is built and applied in
+ * registers ahead of the model (52 B per lane in one launch, against 112 B and three launches for the staged calls).
+ * The outputs select the mode as in bbm_hip_eval_pdf_varying / _table, with the same checks: r == g == b == NULL is
+ * pdf only, pdf == NULL is eval only, neither is both, and a partial r / g / b triple or no output at all is
+ * BBM_HIP_ERR_INVALID_ARG.  cos_in is optional (may be NULL): the cosine of `in` against the normal, 4 B per lane
+ * more.  The normal pointers are required; n == 0 is a no-op; every argument error is returned before any launch.
+ * Arrays that are not all 16-byte aligned take the one-lane kernel.  For lane i, r, g, b and pdf equal, bit for bit,
+ * what these three calls return in sequence with the same mask: bbm_hip_frame_to_local(normal, in),
+ * bbm_hip_frame_to_local(normal, out), the local call on the two results (bbm_hip_eval_pdf, or bbm_hip_eval_pdf_table
+ * with the same call_flags and material); cos_in[i] is the z the first of them returns.  Lane by lane:
+ *   a lane with mask[i] == 0  is the local call's masked lane (component 0) at in = out = (0, 0, 0); cos_in = +0;
+ *   a lane whose normal is not live (|n|^2 <= epsilon(float), NaN)  the same, whatever its mask;
+ *   a table lane with material[i] >= nmaterials  has its component switched off and nothing else, as in the local
+ *                             table call; cos_in is still the transformed z.
+ * Exact and default mode (BBM_HIP_CALL_EXACT / _DEFAULT in the id or in call_flags, or the process switch),
+ * BBM_HIP_RUNTIME_AGGREGATE on a fused aggregate's id, EPD's derived parameters and Merl's table address are the local
+ * call's.  All 49 rows; the table call for the rows bbm_hip_model_has_table reports.  floatRGB only. */
+int bbm_hip_eval_pdf_world(int model_id, const float* params, int nparams,
+                           const float* nx, const float* ny, const float* nz,
+                           const float* in_x, const float* in_y, const float* in_z,
+                           const float* out_x, const float* out_y, const float* out_z,
+                           const uint8_t* mask, size_t n, uint32_t component, uint32_t unit,
+                           float* r, float* g, float* b, float* pdf, float* cos_in, void* stream);
+int bbm_hip_eval_pdf_table_world(const bbm_hip_table* table, int call_flags, const uint32_t* material,
+                                 const float* nx, const float* ny, const float* nz,
+                                 const float* in_x, const float* in_y, const float* in_z,
+                                 const float* out_x, const float* out_y, const float* out_z,
+                                 const uint8_t* mask, size_t n, uint32_t component, uint32_t unit,
+                                 float* r, float* g, float* b, float* pdf, float* cos_in, void* stream);
+
 /* ---------------------------------------------------------------- doubleRGB (Value = double) */
 
 /* The reference's doubleRGB configuration (backbone/native/include/backbone.h:41-42: Value = double, Spectrum =
