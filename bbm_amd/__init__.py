@@ -9,13 +9,13 @@ name, `fromString` / `bsdf_import`, `bsdf_flag`, `unit_t`, `BsdfSample`, and bat
 Importing the package loads the HIP library; if it is missing the import fails loudly.
 """
 from . import _lib
-from .backbone import (Aggregate, AggregateModel, BsdfModel, BsdfSample, MaterialTable, bsdf_flag, bsdf_import, fill_directions, fromString,
+from .backbone import (Aggregate, AggregateModel, BsdfModel, BsdfSample, MaterialPlan, MaterialSet, MaterialTable, bsdf_flag, bsdf_import, fill_directions, fromString,
                        parse_model, model_names, scratch_bytes, scratch_trim, scratch_trim_captured, set_exact_subnormals, to_global, to_local, unit_t, _make_ctor)
 from .models import ATTRIBUTES
 
 _lib.load()
 
-__all__ = ["Aggregate", "AggregateModel", "BsdfModel", "BsdfSample", "MaterialTable", "bsdf_flag", "unit_t", "fromString", "bsdf_import",
+__all__ = ["Aggregate", "AggregateModel", "BsdfModel", "BsdfSample", "MaterialTable", "MaterialSet", "MaterialPlan", "bsdf_flag", "unit_t", "fromString", "bsdf_import",
            "parse_model", "model_names",
            "fill_directions", "scratch_trim", "scratch_trim_captured", "scratch_bytes", "set_exact_subnormals", "to_local", "to_global", "ATTRIBUTES"]
 

@@ -62,6 +62,20 @@ SIGNATURES = {
     "bbm_hip_sample_eval_table_world": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _SZ, _U32, _U32] + [_P] * 12),
     "bbm_hip_eval_pdf_table_world": (_I, [_P, _I, _P] + [_P] * 10 + [_SZ, _U32, _U32] + [_P] * 6),
     "bbm_hip_reflectance_table": (_I, [_P, _I, _P, _P, _P, _P, _P, _SZ, _U32, _U32, _P, _P, _P, _P]),
+    "bbm_hip_set_create": (_I, [_P, _U32, _P]),
+    "bbm_hip_set_destroy": (_I, [_P]),
+    "bbm_hip_set_size": (_U32, [_P]),
+    "bbm_hip_set_rows": (_U32, [_P]),
+    "bbm_hip_set_offset": (_U32, [_P, _U32]),
+    "bbm_hip_set_plan_create": (_I, [_P, _P, _SZ, _P, _P]),
+    "bbm_hip_set_plan_destroy": (_I, [_P]),
+    "bbm_hip_set_plan_lanes": (_SZ, [_P]),
+    "bbm_hip_set_plan_capacity": (_SZ, [_P]),
+    "bbm_hip_set_plan_segments": (_I, [_P, _P, _U32]),
+    "bbm_hip_set_plan_order": (_P, [_P]),
+    "bbm_hip_set_plan_geometry": (_I, [_P, _P]),
+    "bbm_hip_set_eval_pdf": (_I, [_P, _I] + [_P] * 10 + [_SZ, _U32, _U32] + [_P] * 6),
+    "bbm_hip_set_sample_eval": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _SZ, _U32, _U32] + [_P] * 12),
     "bbm_hip_model_has_f64": (_I, [_I]),
     "bbm_hip_eval_pdf_f64": (_I, [_I, _P, _I, _P, _P, _P, _P, _P, _P, _P, _SZ, _U32, _U32, _P, _P, _P, _P, _P]),
     "bbm_hip_sample_f64": (_I, [_I, _P, _I, _P, _P, _P, _P, _P, _P, _SZ, _U32, _U32, _P, _P, _P, _P, _P, _P]),

@@ -1240,6 +1240,215 @@ class MaterialTable:
         return rgb
 
 
+def group_models(models):
+    """MaterialSet.from_models' grouping, with no table made: BsdfModels or model strings of any rows ->
+    (groups, material_ids).  groups: one (name, runtime, [models]) per (model_id, runtime) in order of first
+    appearance; material_ids: int32, the global id of each input model in input order (table k's ids follow table
+    k - 1's).  Rows without table kernels and composed aggregates are refused as MaterialTable refuses them."""
+    ms = [fromString(m) if isinstance(m, str) else m for m in models]
+    if not ms:
+        raise ValueError("MaterialSet.from_models: no models")
+    groups, where = [], {}
+    for m in ms:
+        if isinstance(m, AggregateModel):
+            raise NotImplementedError("MaterialTable: composed aggregates have no material tables (fused "
+                                      "Aggregate(Lambertian, X) models do)")
+        if not isinstance(m, BsdfModel):
+            raise TypeError("MaterialSet.from_models: expected BsdfModels or model strings")
+        if not m.has_table():
+            raise _lib.BackboneError(_lib.ERR_UNSUPPORTED, f"{m.name}: no material-table kernels")
+        key = (m.model_id, m.runtime)
+        if key not in where:
+            where[key] = len(groups)
+            groups.append((m.name, m.runtime, []))
+        groups[where[key]][2].append(m)
+    first = np.concatenate([[0], np.cumsum([len(g[2]) for g in groups])])
+    seen = [0] * len(groups)
+    ids = np.empty(len(ms), dtype=np.int32)
+    for i, m in enumerate(ms):
+        k = where[(m.model_id, m.runtime)]
+        ids[i] = first[k] + seen[k]
+        seen[k] += 1
+    return groups, ids
+
+
+class _DevicePtr:
+    """Device memory of the library as a CUDA array, for torch.as_tensor."""
+
+    def __init__(self, ptr, count):
+        self.__cuda_array_interface__ = {"shape": (count,), "typestr": "<i4", "data": (ptr, False), "version": 2}
+
+
+class MaterialPlan:
+    """The stable partition of one batch's lanes by table (bbm_hip_set_plan_*), made by
+    MaterialSet.plan and passed as `plan=` to any number of calls over the same hits."""
+
+    def __init__(self, mset, material, stream=None):
+        torch = _torch()
+        self._handle = None
+        if not isinstance(material, torch.Tensor) or material.dim() != 1:
+            raise TypeError("material: expected a 1-D int32 CUDA tensor")
+        n = material.numel()
+        idx = MaterialTable._material(material, n, material.device)
+        _on_stream(stream, material)
+        handle = ctypes.c_void_p()
+        _lib.check(_lib.load().bbm_hip_set_plan_create(mset._live(), idx, n, _stream_ptr(stream), ctypes.byref(handle)))
+        self._handle = handle
+        self.set = mset
+        self.device = material.device
+        self.lanes = n
+        seg = (ctypes.c_uint64 * (mset.rows + 1))()
+        _lib.check(_lib.load().bbm_hip_set_plan_segments(handle, seg, mset.rows + 1))
+        self.segments = [int(v) for v in seg]
+
+    def _live(self):
+        if self._handle is None:
+            raise ValueError("MaterialPlan: the plan is closed")
+        self.set._live()
+        return self._handle
+
+    def order(self):
+        """The source lane of every sorted slot: an int32 CUDA tensor of the plan's capacity, -1 in padding slots."""
+        torch = _torch()
+        h = self._live()
+        cap = self.segments[-1]
+        if cap == 0:
+            return torch.empty((0,), dtype=torch.int32, device=self.device)
+        ptr = _lib.load().bbm_hip_set_plan_order(h)
+        with torch.cuda.device(self.device):
+            return torch.as_tensor(_DevicePtr(ptr, cap), device=self.device).clone()
+
+    def close(self):
+        """Release the plan's device memory (waits for the device: calls already enqueued finish first)."""
+        h, self._handle = self._handle, None
+        if h is not None:
+            _lib.load().bbm_hip_set_plan_destroy(h)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:       # interpreter shutdown
+            pass
+
+
+class MaterialSet:
+    """Material tables of different models behind one global material id per lane (bbm_hip_set_*):
+    table k owns the ids [offsets[k], offsets[k + 1]).  eval_pdf / eval / pdf / sample_eval take MaterialTable's
+    arguments with `material=` (global ids, an int32 CUDA tensor) or `plan=` (a MaterialPlan of the same hits, made
+    once by plan() and shared by several calls), and return the same shapes; lane i gets exactly what its table's call
+    returns for it.  An id out of range is table 0's masked-index lane.  The set keeps its tables alive."""
+
+    def __init__(self, tables):
+        self._handle = None
+        tables = list(tables)
+        if not all(isinstance(t, MaterialTable) for t in tables):
+            raise TypeError("MaterialSet: expected MaterialTables")
+        arr = (ctypes.c_void_p * max(len(tables), 1))(*[t._live().value for t in tables])
+        handle = ctypes.c_void_p()
+        _lib.check(_lib.load().bbm_hip_set_create(arr, len(tables), ctypes.byref(handle)))
+        self._handle = handle
+        self.tables = tables
+        self.material_ids = None
+        lib = _lib.load()
+        self.rows = int(lib.bbm_hip_set_rows(handle))
+        self.offsets = [int(lib.bbm_hip_set_offset(handle, k)) for k in range(self.rows + 1)]
+
+    @classmethod
+    def from_models(cls, models, *, stream=None):
+        """A set of BsdfModels or model strings of different rows: one MaterialTable per (model, runtime) group in
+        order of first appearance; `material_ids` holds each input model's global id, in input order."""
+        groups, ids = group_models(models)
+        s = cls([MaterialTable.from_models(ms, stream=stream) for _, _, ms in groups])
+        s.material_ids = ids
+        return s
+
+    def __len__(self):
+        return self.offsets[-1]
+
+    def close(self):
+        """Release the set (not its tables, which other sets may share)."""
+        h, self._handle = self._handle, None
+        if h is not None:
+            _lib.load().bbm_hip_set_destroy(h)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:       # interpreter shutdown
+            pass
+
+    def _live(self):
+        if self._handle is None:
+            raise ValueError("MaterialSet: the set is closed")
+        return self._handle
+
+    def plan(self, material, stream=None):
+        """Partition one batch's lanes by table: a MaterialPlan for `plan=`.  Waits for the stream once."""
+        return MaterialPlan(self, material, stream)
+
+    def _planned(self, material, plan, stream, n, device):
+        """(the plan to use, whether it is this call's own)."""
+        if (material is None) == (plan is None):
+            raise ValueError("MaterialSet: give material= (global ids) or plan= (a MaterialPlan), not both")
+        self._live()
+        if plan is None:
+            MaterialTable._material(material, n, device)
+            return MaterialPlan(self, material, stream), True
+        if not isinstance(plan, MaterialPlan) or plan.set is not self:
+            raise ValueError("plan: expected a MaterialPlan made by this set")
+        plan._live()
+        return plan, False
+
+    def eval_pdf(self, in_, out, component=bsdf_flag.All, unit=unit_t.Radiance, mask=None, *, material=None,
+                 plan=None, rgb=None, pdf=None, stream=None, mode=3, exact=None, normal=None, cosine=False):
+        nptr = _world_normal(normal, cosine, None, in_, out)
+        if _is_f64(in_) or _is_f64(out):
+            raise TypeError("MaterialSet: material sets are floatRGB only (float32 tensors)")
+        ix, iy, iz, n = _soa(in_, what="in")
+        ox, oy, oz, _ = _soa(out, n, what="out")
+        dev = _device(in_)
+        mptr, _keep = _mask_ptr(mask, n)
+        rgb, pdf = _eval_pdf_outputs(mode, n, dev, rgb, pdf)
+        cos = _torch().empty((n,), dtype=_torch().float32, device=dev) if cosine else None
+        _on_stream(stream, _keep, rgb, pdf, cos)
+        p, own = self._planned(material, plan, stream, n, dev)
+        try:
+            _lib.check(_lib.load().bbm_hip_set_eval_pdf(
+                p._live(), MaterialTable._flags(exact), *(nptr or (None, None, None)), ix, iy, iz, ox, oy, oz, mptr, n,
+                int(component), int(unit), *_eval_pdf_ptrs(mode, rgb, pdf), None if cos is None else cos.data_ptr(),
+                _stream_ptr(stream)))
+        finally:
+            if own:
+                p.close()
+        return (rgb, pdf, cos) if cosine else (rgb, pdf)
+
+    def eval(self, in_, out, component=bsdf_flag.All, unit=unit_t.Radiance, mask=None, **kw):
+        return _with_cosine(self.eval_pdf(in_, out, component, unit, mask, mode=1, **kw), 0, kw.get("cosine", False))
+
+    def pdf(self, in_, out, component=bsdf_flag.All, unit=unit_t.Radiance, mask=None, **kw):
+        return _with_cosine(self.eval_pdf(in_, out, component, unit, mask, mode=2, **kw), 1, kw.get("cosine", False))
+
+    def sample_eval(self, out, xi, component=bsdf_flag.All, unit=unit_t.Radiance, mask=None, *, material=None,
+                    plan=None, value=True, weight=True, stream=None, exact=None, normal=None):
+        nptr = None if normal is None else _normal_rows(normal, out)
+        ox, oy, oz, n, x0, x1 = _sample_eval_inputs(out, xi)
+        dev = x0.device
+        mptr, _keep = _mask_ptr(mask, n)
+        outs = _sample_eval_outputs(n, dev, value, weight)
+        _on_stream(stream, _keep, *outs)
+        d, p_, f, v, w = outs
+        p, own = self._planned(material, plan, stream, n, dev)
+        try:
+            _lib.check(_lib.load().bbm_hip_set_sample_eval(
+                p._live(), MaterialTable._flags(exact), *(nptr or (None, None, None)), ox, oy, oz, x0.data_ptr(),
+                x1.data_ptr(), mptr, n, int(component), int(unit), d[0].data_ptr(), d[1].data_ptr(), d[2].data_ptr(),
+                p_.data_ptr(), f.data_ptr(), *_row_ptrs(v), *_row_ptrs(w), _stream_ptr(stream)))
+        finally:
+            if own:
+                p.close()
+        return BsdfSample(d, p_, f), v, w
+
+
 def _make_ctor(name):
     def ctor(*args, **kwargs):
         return BsdfModel(name, *args, **kwargs)

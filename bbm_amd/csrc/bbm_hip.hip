@@ -13,6 +13,7 @@
 #include "registry.hpp"
 #include "aggregate.hpp"  // kAggregateModeSlot
 #include "merl.hpp"       // bbm_hip_merl_table
+#include "set.hpp"        // the material sets' plan, gather and scatter launchers
 
 namespace bbmhip {
 
@@ -824,6 +825,351 @@ int bbm_hip_reflectance_table(const bbm_hip_table* t, int call_flags, const uint
   a.e.p = t->first_raw;
   a.src = {t->raw, material, t->count};
   return t->e->run.reflectance_tab(a, static_cast<hipStream_t>(stream));
+}
+
+// ------------------------------------------------------------------------------- material sets (set.hpp)
+
+}  // extern "C"
+
+// An ordered list of tables addressed by one global id per lane: table k owns [rows.off[k], rows.off[k + 1]).
+struct bbm_hip_set
+{
+  std::vector<const bbm_hip_table*> tables;
+  SetRows rows;
+};
+
+// The stable partition of n lanes by table.  src and local are one device allocation of 2 x slots uint32; seg is the
+// host copy of the segment starts (seg[rows] = capacity <= slots).
+struct bbm_hip_set_plan
+{
+  const bbm_hip_set* set;
+  uint32_t n, slots;
+  uint32_t* src;
+  uint32_t* local;
+  uint32_t seg[kSetMaxRows + 1];
+};
+
+namespace {
+
+// What the two calls on a plan check first; *done is set where nothing is left to do (n == 0).
+int set_call(const bbm_hip_set_plan* p, int call_flags, size_t n, bool& done)
+{
+  done = false;
+  if (!p) return fail(BBM_HIP_ERR_INVALID_ARG, "plan is NULL");
+  if (const int rc = table_call(p->set->tables[0], call_flags, 0, nullptr)) return rc;
+  if (n != p->n)
+    return fail(BBM_HIP_ERR_INVALID_ARG, "n is " + std::to_string(n) + ", the plan was made for " + std::to_string(p->n) + " lanes");
+  done = n == 0;
+  return BBM_HIP_OK;
+}
+
+// all three normal pointers (the world call), none (the local call); a mixture is an error
+int set_normal(const float* nx, const float* ny, const float* nz, bool& world)
+{
+  world = nx && ny && nz;
+  if (!world && (nx || ny || nz)) return fail(BBM_HIP_ERR_INVALID_ARG, "normal: give nx, ny and nz or none");
+  return BBM_HIP_OK;
+}
+
+// The sorted buffers of one call: `streams` arrays of capacity four-byte slots and the mask bytes, one scratch block.
+struct SetScratch
+{
+  char* base = nullptr;
+  size_t used = 0, stride = 0;
+  hipStream_t s = nullptr;
+  int acquire(uint32_t capacity, int streams, bool mask, hipStream_t stream)
+  {
+    s = stream;
+    stride = size_t(capacity) * 4u;
+    base = static_cast<char*>(scratch_acquire(stride * size_t(streams) + (mask ? capacity : 0u), s));
+    return base ? BBM_HIP_OK : fail(BBM_HIP_ERR_HIP, "material set scratch: " + scratch_failure());
+  }
+  template<class T> T* take(size_t bytes) { T* p = reinterpret_cast<T*>(base + used); used += bytes; return p; }
+  float* stream4() { return take<float>(stride); }
+  ~SetScratch() { if (base) scratch_release(base, s); }
+};
+
+// a caller stream and its sorted twin, entered into a gather (lane -> slot) or a scatter (slot -> lane)
+void move_in(SetMoveArgs& m, const void* lanes, void* sorted)
+{
+  m.from[m.count] = static_cast<const uint32_t*>(lanes);
+  m.to[m.count++] = static_cast<uint32_t*>(sorted);
+}
+void move_out(SetMoveArgs& m, void* sorted, void* lanes)
+{
+  m.from[m.count] = static_cast<const uint32_t*>(sorted);
+  m.to[m.count++] = static_cast<uint32_t*>(lanes);
+}
+
+}  // namespace
+
+extern "C" {
+
+int bbm_hip_set_create(const bbm_hip_table* const* tables, uint32_t ntables, bbm_hip_set** out)
+{
+  if (!tables) return fail(BBM_HIP_ERR_INVALID_ARG, "tables is NULL");
+  if (ntables == 0 || ntables > kSetMaxRows)
+    return fail(BBM_HIP_ERR_INVALID_ARG, "a material set holds 1 to 32 tables, got " + std::to_string(ntables));
+  if (!out) return fail(BBM_HIP_ERR_INVALID_ARG, "out is NULL");
+  *out = nullptr;
+  uint64_t total = 0;
+  for (uint32_t k = 0; k < ntables; ++k)
+  {
+    if (!tables[k]) return fail(BBM_HIP_ERR_INVALID_ARG, "table " + std::to_string(k) + " is NULL");
+    total += tables[k]->count;
+  }
+  if (total >= 0xFFFFFFFFull)
+    return fail(BBM_HIP_ERR_INVALID_ARG, "a material set holds fewer than 2^32 - 1 materials, got " + std::to_string(total));
+  std::unique_ptr<bbm_hip_set> s(new bbm_hip_set);
+  std::memset(&s->rows, 0, sizeof(s->rows));
+  s->rows.rows = ntables;
+  for (uint32_t k = 0; k < ntables; ++k)
+  {
+    s->tables.push_back(tables[k]);
+    s->rows.off[k + 1] = s->rows.off[k] + tables[k]->count;
+  }
+  *out = s.release();
+  return BBM_HIP_OK;
+}
+
+int bbm_hip_set_destroy(bbm_hip_set* set)
+{
+  delete set;      // a set owns no device memory: its offsets travel in the kernarg
+  return BBM_HIP_OK;
+}
+
+uint32_t bbm_hip_set_size(const bbm_hip_set* set) { return set ? set->rows.off[set->rows.rows] : 0u; }
+
+uint32_t bbm_hip_set_rows(const bbm_hip_set* set) { return set ? set->rows.rows : 0u; }
+
+uint32_t bbm_hip_set_offset(const bbm_hip_set* set, uint32_t k)
+{
+  return set && k <= set->rows.rows ? set->rows.off[k] : 0xFFFFFFFFu;
+}
+
+int bbm_hip_set_plan_geometry(uint32_t* tile, uint32_t* scan_chunk)
+{
+  if (tile) *tile = kSetTile;
+  if (scan_chunk) *scan_chunk = kSetScanChunk;
+  return BBM_HIP_OK;
+}
+
+int bbm_hip_set_plan_create(const bbm_hip_set* set, const uint32_t* material, size_t n, void* stream,
+                            bbm_hip_set_plan** out)
+{
+  if (!set) return fail(BBM_HIP_ERR_INVALID_ARG, "set is NULL");
+  if (!out) return fail(BBM_HIP_ERR_INVALID_ARG, "out is NULL");
+  *out = nullptr;
+  if (n > 0 && !material) return fail(BBM_HIP_ERR_INVALID_ARG, "material index pointer is NULL");
+  const uint32_t rows = set->rows.rows;
+  if (uint64_t(n) + 4ull * rows + 4ull >= 0xFFFFFFFFull)
+    return fail(BBM_HIP_ERR_INVALID_ARG, "batch too large for one plan");
+  std::unique_ptr<bbm_hip_set_plan> p(new bbm_hip_set_plan);
+  std::memset(p.get(), 0, sizeof(*p));
+  p->set = set;
+  p->n = uint32_t(n);
+  if (n == 0)
+  {
+    *out = p.release();
+    return BBM_HIP_OK;
+  }
+  const hipStream_t s = static_cast<hipStream_t>(stream);
+  p->slots = ((p->n + 3u) & ~3u) + 4u * rows;
+  SetPlanArgs a;
+  std::memset(&a, 0, sizeof(a));
+  a.rows = set->rows;
+  a.material = material;
+  a.n = p->n;
+  a.groups = (p->n + kSetTile - 1) / kSetTile;
+  a.slots = p->slots;
+  hipError_t err = hipMalloc(reinterpret_cast<void**>(&p->src), size_t(p->slots) * 8u);
+  if (err != hipSuccess)
+  {
+    (void)hipGetLastError();
+    return fail(BBM_HIP_ERR_HIP, std::string("material plan allocation failed: ") + hipGetErrorString(err));
+  }
+  p->local = p->src + p->slots;
+  a.src = p->src;
+  a.local = p->local;
+  // the counts and the layout record: scratch of this call
+  const size_t count_bytes = (size_t(rows) * a.groups * 4u + 15u) & ~size_t(15);
+  char* tmp = static_cast<char*>(scratch_acquire(count_bytes + sizeof(SetMeta), s));
+  int rc = tmp ? BBM_HIP_OK : fail(BBM_HIP_ERR_HIP, "material plan scratch: " + scratch_failure());
+  if (!rc)
+  {
+    a.counts = reinterpret_cast<uint32_t*>(tmp);
+    a.meta = reinterpret_cast<SetMeta*>(tmp + count_bytes);
+    rc = set_plan_launch(a, s);
+    if (!rc)
+    {
+      // the one host wait of the feature: the segment starts decide the per-row launches of every call on the plan
+      err = hipMemcpyAsync(p->seg, a.meta->seg, (rows + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost, s);
+      if (err == hipSuccess) err = hipStreamSynchronize(s);
+      if (err != hipSuccess)
+      {
+        (void)hipGetLastError();
+        rc = fail(BBM_HIP_ERR_HIP, std::string("material plan failed: ") + hipGetErrorString(err));
+      }
+    }
+    scratch_release(tmp, s);
+  }
+  for (uint32_t k = 0; !rc && k < rows; ++k)
+    if (p->seg[k] > p->seg[k + 1] || (p->seg[k] & 3u) || p->seg[rows] > p->slots || (p->seg[rows] & 3u))
+      rc = fail(BBM_HIP_ERR_HIP, "material plan: inconsistent segment offsets");
+  if (rc)
+  {
+    (void)hipFree(p->src);
+    return rc;
+  }
+  *out = p.release();
+  return BBM_HIP_OK;
+}
+
+int bbm_hip_set_plan_destroy(bbm_hip_set_plan* plan)
+{
+  if (!plan) return BBM_HIP_OK;
+  // hipFree waits for the device, so calls already enqueued on the plan finish first
+  const hipError_t err = plan->src ? hipFree(plan->src) : hipSuccess;
+  delete plan;
+  if (err != hipSuccess) return fail(BBM_HIP_ERR_HIP, std::string("hipFree failed: ") + hipGetErrorString(err));
+  return BBM_HIP_OK;
+}
+
+size_t bbm_hip_set_plan_lanes(const bbm_hip_set_plan* plan) { return plan ? plan->n : 0u; }
+
+size_t bbm_hip_set_plan_capacity(const bbm_hip_set_plan* plan) { return plan ? plan->seg[plan->set->rows.rows] : 0u; }
+
+int bbm_hip_set_plan_segments(const bbm_hip_set_plan* plan, uint64_t* out, uint32_t count)
+{
+  if (!plan) return fail(BBM_HIP_ERR_INVALID_ARG, "plan is NULL");
+  const uint32_t have = plan->set->rows.rows + 1;
+  if (!out || count < have)
+    return fail(BBM_HIP_ERR_INVALID_ARG, "segments: room for " + std::to_string(have) + " offsets is needed");
+  for (uint32_t k = 0; k < have; ++k) out[k] = plan->seg[k];
+  return int(have);
+}
+
+const uint32_t* bbm_hip_set_plan_order(const bbm_hip_set_plan* plan) { return plan ? plan->src : nullptr; }
+
+int bbm_hip_set_eval_pdf(const bbm_hip_set_plan* plan, int call_flags,
+                         const float* nx, const float* ny, const float* nz,
+                         const float* in_x, const float* in_y, const float* in_z,
+                         const float* out_x, const float* out_y, const float* out_z,
+                         const uint8_t* mask, size_t n, uint32_t component, uint32_t unit,
+                         float* r, float* g, float* b, float* pdf, float* cos_in, void* stream)
+{
+  bool done, world;
+  int rc = set_call(plan, call_flags, n, done);
+  if (rc || done) return rc;
+  if ((rc = set_normal(nx, ny, nz, world))) return rc;
+  if (cos_in && !world) return fail(BBM_HIP_ERR_INVALID_ARG, "cos_in needs a normal: it is the cosine of `in` against it");
+  EvalArgs checked;
+  int mode = 0;
+  if ((rc = eval_args(mode, in_x, in_y, in_z, out_x, out_y, out_z, mask, n, component, r, g, b, pdf, checked))) return rc;
+  const bbm_hip_set& set = *plan->set;
+  const uint32_t rows = set.rows.rows, capacity = plan->seg[rows];
+  for (uint32_t k = 0; world && k < rows; ++k)
+    if (!set.tables[k]->e->run.eval_pdf_tab_world)
+      return fail(BBM_HIP_ERR_UNSUPPORTED, std::string(set.tables[k]->e->name) + ": no material-table kernels");
+  const hipStream_t s = static_cast<hipStream_t>(stream);
+  const bool eval = mode & kModeEval, want_pdf = mode & kModePdf;
+  SetScratch scratch;
+  if ((rc = scratch.acquire(capacity, (world ? 9 : 6) + (eval ? 3 : 0) + (want_pdf ? 1 : 0) + (cos_in ? 1 : 0),
+                            mask != nullptr, s)))
+    return rc;
+  SetMoveArgs in, out;
+  std::memset(&in, 0, sizeof(in));
+  in.src = plan->src; in.n = plan->n; in.capacity = capacity;
+  out = in;
+  const float* lanes[9] = {nx, ny, nz, in_x, in_y, in_z, out_x, out_y, out_z};
+  float* sorted[9] = {};
+  for (int c = world ? 0 : 3; c < 9; ++c) move_in(in, lanes[c], sorted[c] = scratch.stream4());
+  float* res[5] = {r, g, b, pdf, cos_in};
+  float* sres[5] = {};
+  for (int c = 0; c < 5; ++c)
+    if (res[c]) move_out(out, sres[c] = scratch.stream4(), res[c]);
+  uint8_t* smask = mask ? scratch.take<uint8_t>(capacity) : nullptr;
+  in.mask_from = mask; in.mask_to = smask;
+  if ((rc = set_gather_launch(in, s))) return rc;
+  for (uint32_t k = 0; k < rows; ++k)
+  {
+    const size_t o = plan->seg[k], nk = plan->seg[k + 1] - o;
+    if (nk == 0) continue;
+    const auto at = [o](float* p) { return p ? p + o : nullptr; };
+    const uint8_t* mk = smask ? smask + o : nullptr;
+    if (world)
+      rc = bbm_hip_eval_pdf_table_world(set.tables[k], call_flags, plan->local + o, sorted[0] + o, sorted[1] + o,
+                                        sorted[2] + o, sorted[3] + o, sorted[4] + o, sorted[5] + o, sorted[6] + o,
+                                        sorted[7] + o, sorted[8] + o, mk, nk, component, unit, at(sres[0]), at(sres[1]),
+                                        at(sres[2]), at(sres[3]), at(sres[4]), stream);
+    else
+      rc = bbm_hip_eval_pdf_table(set.tables[k], call_flags, plan->local + o, sorted[3] + o, sorted[4] + o,
+                                  sorted[5] + o, sorted[6] + o, sorted[7] + o, sorted[8] + o, mk, nk, component, unit,
+                                  at(sres[0]), at(sres[1]), at(sres[2]), at(sres[3]), stream);
+    if (rc) return rc;
+  }
+  return set_scatter_launch(out, s);
+}
+
+int bbm_hip_set_sample_eval(const bbm_hip_set_plan* plan, int call_flags,
+                            const float* nx, const float* ny, const float* nz,
+                            const float* out_x, const float* out_y, const float* out_z,
+                            const float* xi0, const float* xi1,
+                            const uint8_t* mask, size_t n, uint32_t component, uint32_t unit,
+                            float* dir_x, float* dir_y, float* dir_z, float* pdf, uint32_t* flag,
+                            float* r, float* g, float* b, float* wr, float* wg, float* wb, void* stream)
+{
+  bool done, world;
+  int rc = set_call(plan, call_flags, n, done);
+  if (rc || done) return rc;
+  if ((rc = set_normal(nx, ny, nz, world))) return rc;
+  SampleEvalArgs checked;
+  if ((rc = sample_eval_args(out_x, out_y, out_z, xi0, xi1, mask, n, component, dir_x, dir_y, dir_z, pdf, flag,
+                             r, g, b, wr, wg, wb, checked)))
+    return rc;
+  const bbm_hip_set& set = *plan->set;
+  const uint32_t rows = set.rows.rows, capacity = plan->seg[rows];
+  for (uint32_t k = 0; k < rows; ++k)
+    if (!set.tables[k]->e->run.sample_eval_tab || (world && !set.tables[k]->e->run.sample_eval_tab_world))
+      return fail(BBM_HIP_ERR_UNSUPPORTED, std::string(set.tables[k]->e->name) + ": no material-table kernels");
+  const hipStream_t s = static_cast<hipStream_t>(stream);
+  SetScratch scratch;
+  if ((rc = scratch.acquire(capacity, (world ? 8 : 5) + 5 + (r ? 3 : 0) + (wr ? 3 : 0), mask != nullptr, s))) return rc;
+  SetMoveArgs in, out;
+  std::memset(&in, 0, sizeof(in));
+  in.src = plan->src; in.n = plan->n; in.capacity = capacity;
+  out = in;
+  const float* lanes[8] = {nx, ny, nz, out_x, out_y, out_z, xi0, xi1};
+  float* sorted[8] = {};
+  for (int c = world ? 0 : 3; c < 8; ++c) move_in(in, lanes[c], sorted[c] = scratch.stream4());
+  void* res[11] = {dir_x, dir_y, dir_z, pdf, flag, r, g, b, wr, wg, wb};
+  float* sres[11] = {};
+  for (int c = 0; c < 11; ++c)
+    if (res[c]) move_out(out, sres[c] = scratch.stream4(), res[c]);
+  uint8_t* smask = mask ? scratch.take<uint8_t>(capacity) : nullptr;
+  in.mask_from = mask; in.mask_to = smask;
+  if ((rc = set_gather_launch(in, s))) return rc;
+  for (uint32_t k = 0; k < rows; ++k)
+  {
+    const size_t o = plan->seg[k], nk = plan->seg[k + 1] - o;
+    if (nk == 0) continue;
+    const auto at = [o](float* p) { return p ? p + o : nullptr; };
+    const uint8_t* mk = smask ? smask + o : nullptr;
+    uint32_t* fl = reinterpret_cast<uint32_t*>(sres[4]) + o;
+    if (world)
+      rc = bbm_hip_sample_eval_table_world(set.tables[k], call_flags, plan->local + o, sorted[0] + o, sorted[1] + o,
+                                           sorted[2] + o, sorted[3] + o, sorted[4] + o, sorted[5] + o, sorted[6] + o,
+                                           sorted[7] + o, mk, nk, component, unit, at(sres[0]), at(sres[1]), at(sres[2]),
+                                           at(sres[3]), fl, at(sres[5]), at(sres[6]), at(sres[7]), at(sres[8]),
+                                           at(sres[9]), at(sres[10]), stream);
+    else
+      rc = bbm_hip_sample_eval_table(set.tables[k], call_flags, plan->local + o, sorted[3] + o, sorted[4] + o,
+                                     sorted[5] + o, sorted[6] + o, sorted[7] + o, mk, nk, component, unit, at(sres[0]),
+                                     at(sres[1]), at(sres[2]), at(sres[3]), fl, at(sres[5]), at(sres[6]), at(sres[7]),
+                                     at(sres[8]), at(sres[9]), at(sres[10]), stream);
+    if (rc) return rc;
+  }
+  return set_scatter_launch(out, s);
 }
 
 // ------------------------------------------------------------------------------- doubleRGB (f64.hip)

@@ -331,6 +331,70 @@ int bbm_hip_eval_pdf_table_world(const bbm_hip_table* table, int call_flags, con
                                  const uint8_t* mask, size_t n, uint32_t component, uint32_t unit,
                                  float* r, float* g, float* b, float* pdf, float* cos_in, void* stream);
 
+/* ---------------------------------------------------------------- material sets: tables of different models */
+
+/* One call over hits whose materials are different models (a wavefront renderer shading with CookTorrance, GGX and
+ * Lambertian aggregates side by side).  A set is an ordered list of 1 to 32 material tables, of any rows (the same row
+ * may appear more than once), addressed by one GLOBAL material id per lane: table k owns the ids
+ * [off[k], off[k] + size(k)), off[0] = 0, and the total is below 2^32 - 1.  For lane i with id g in range, row(i) is
+ * the table that owns g and local(i) = g - off[row(i)]; for g >= total (a negative int32 included) row(i) = 0 and
+ * local(i) = 0xFFFFFFFF, table 0's masked-index lane.  Every output of lane i equals, bit for bit, what the matching
+ * table call (bbm_hip_eval_pdf_table, _eval_pdf_table_world, _sample_eval_table, _sample_eval_table_world) returns for
+ * that lane on table row(i) with index local(i), given the lane's own inputs, mask byte, component, unit and
+ * call_flags.  Modes, exact / default mode, a runtime aggregate baked into a table, the world calls' rules for masked
+ * lanes and normals that are not live, and the optional cosine are therefore the table calls'.
+ *
+ * Two steps, because a renderer's next-event estimation and its bounce share their hits:
+ *   bbm_hip_set_plan_create partitions n lanes by table, stably (within a table's segment the source lanes ascend, so
+ *     hits that arrive sorted by material stay coherent), into device memory the plan owns: src[j], the source lane of
+ *     sorted slot j (0xFFFFFFFF in a padding slot), and the table index of slot j.  Every segment starts at a multiple
+ *     of four slots (at most 3 padding slots per table), so each table's slice of a 16-byte aligned buffer is aligned.
+ *     Create copies the ntables + 1 segment offsets to the host and WAITS FOR THE STREAM ONCE: the only host wait of
+ *     material sets.  For that reason a plan cannot be created while its stream is being captured into a graph.
+ *   bbm_hip_set_eval_pdf / bbm_hip_set_sample_eval gather the input streams into sorted buffers (stream-ordered
+ *     scratch of the library), run the table entry point of every table that has lanes on its slice, and scatter the
+ *     outputs back through src.  Stream-ordered, no host wait.  nx == ny == nz == NULL selects the local call, all three
+ *     the world call, a mixture is BBM_HIP_ERR_INVALID_ARG; cos_in needs a normal.  The output groups select what is
+ *     computed exactly as in the table calls, with their checks.  n must be the plan's n.
+ * Lifetimes: a plan refers to its set and the set to its tables; destroy the plan, then the set, then the tables.
+ * Using a destroyed handle is the caller's error.  bbm_hip_set_plan_destroy frees with hipFree (it waits for the
+ * device, so enqueued calls finish first); a set owns no device memory.  NULL is a no-op for both.
+ * Every argument error (a NULL handle, ntables of 0 or above 32, a NULL table, a total that overflows, another n than
+ * the plan's, a partial normal, cos_in without a normal, no output group) is returned before any allocation, copy or
+ * launch.  n == 0 is valid: the plan is empty and the calls return BBM_HIP_OK with nothing launched.
+ * Not available on a set: sample alone and reflectance.  floatRGB only. */
+typedef struct bbm_hip_set bbm_hip_set;
+typedef struct bbm_hip_set_plan bbm_hip_set_plan;
+int bbm_hip_set_create(const bbm_hip_table* const* tables, uint32_t ntables, bbm_hip_set** out);
+int bbm_hip_set_destroy(bbm_hip_set* set);
+uint32_t bbm_hip_set_size(const bbm_hip_set* set);                 /* the total number of materials */
+uint32_t bbm_hip_set_rows(const bbm_hip_set* set);                 /* ntables */
+uint32_t bbm_hip_set_offset(const bbm_hip_set* set, uint32_t k);   /* off[k], k <= ntables; else 0xFFFFFFFF */
+int bbm_hip_set_plan_create(const bbm_hip_set* set, const uint32_t* material, size_t n, void* stream,
+                            bbm_hip_set_plan** out);
+int bbm_hip_set_plan_destroy(bbm_hip_set_plan* plan);
+size_t bbm_hip_set_plan_lanes(const bbm_hip_set_plan* plan);       /* n */
+size_t bbm_hip_set_plan_capacity(const bbm_hip_set_plan* plan);    /* sorted slots, padding included */
+/* the ntables + 1 segment offsets (slots); returns their number, count must be at least that */
+int bbm_hip_set_plan_segments(const bbm_hip_set_plan* plan, uint64_t* out, uint32_t count);
+/* src: DEVICE memory of `capacity` uint32, valid until the plan is destroyed (NULL for an empty plan) */
+const uint32_t* bbm_hip_set_plan_order(const bbm_hip_set_plan* plan);
+/* the lanes one workgroup ranks at once, and the entries one pass of the offset scan's loop covers */
+int bbm_hip_set_plan_geometry(uint32_t* tile, uint32_t* scan_chunk);
+int bbm_hip_set_eval_pdf(const bbm_hip_set_plan* plan, int call_flags,
+                         const float* nx, const float* ny, const float* nz,
+                         const float* in_x, const float* in_y, const float* in_z,
+                         const float* out_x, const float* out_y, const float* out_z,
+                         const uint8_t* mask, size_t n, uint32_t component, uint32_t unit,
+                         float* r, float* g, float* b, float* pdf, float* cos_in, void* stream);
+int bbm_hip_set_sample_eval(const bbm_hip_set_plan* plan, int call_flags,
+                            const float* nx, const float* ny, const float* nz,
+                            const float* out_x, const float* out_y, const float* out_z,
+                            const float* xi0, const float* xi1,
+                            const uint8_t* mask, size_t n, uint32_t component, uint32_t unit,
+                            float* dir_x, float* dir_y, float* dir_z, float* pdf, uint32_t* flag,
+                            float* r, float* g, float* b, float* wr, float* wg, float* wb, void* stream);
+
 /* ---------------------------------------------------------------- doubleRGB (Value = double) */
 
 /* The reference's doubleRGB configuration (backbone/native/include/backbone.h:41-42: Value = double, Spectrum =
