@@ -185,7 +185,8 @@ struct EpdNdf
     __builtin_memcpy(&pb, &p, 4);
     const float g = (tag == pb && pb != 0u) ? q[kGammaSlot] : float(tgamma(double(div_nr(1.0f, p))));
     const float n = (p > kEpsF) ? (p * kInvPiF) * div_nr(1.0f, g) : 0.0f;
-    normalization = div_nr(n, beta * beta);
+    // the reference returns its 0 before "result /= beta * beta" (epd.h:164-165): p <= eps with beta = 0 is 0, not 0 / 0
+    normalization = (p > kEpsF) ? div_nr(n, beta * beta) : 0.0f;
     inv_p = div_nr(1.0f, p);
   }
 
@@ -230,7 +231,12 @@ struct EpdNdf
     if (!((xi0 >= 0) && (xi1 >= 0) && (xi0 <= 1) && (xi1 <= 1))) return mk3(0.0f, 0.0f, 0.0f);
     float sp, cp;
     cossin_cr(kPi2F * xi0, cp, sp);
-    const float g = float(gamma_q_inv_d(double(inv_p), double(xi1)));
+    // xi1 = 1: the reference's gamma_q_inv(a, q = 1) starts its Halley iteration at p = 0, x = 0, where
+    // t = (P - p) / R(a, 0) = 0 / 0 (util/invgamma.h:404-414): its sampled normal is NaN, and so is this one (f64.hpp)
+    // p = 0: a = 1 / p is infinite and the reference's initial estimate is inf - inf for every xi1 in (0, 1): NaN
+    // there too (xi1 = 0 is its early return, as here)
+    const bool undefined = (xi1 >= 1.0f) || (inv_p > 3.40282347e38f && xi1 > 0.0f);
+    const float g = undefined ? __builtin_nanf("") : float(gamma_q_inv_d(double(inv_p), double(xi1)));
     const float tan2 = beta * beta * powf_glibc(g, inv_p);      // glibc powf (epd.h:100)
     const float cosT = float(1.0 / sqrt(1.0 + double(tan2)));          // rsqrt(1.0 + tan2) in double, stored as Value
     const float sinT = float(safe_sqrt(1.0 - double(cosT * cosT)));

@@ -851,7 +851,12 @@ struct Lafortune
     sincos(xi0 * (2.0 * kPi), &sp, &cp);
     const double cosT = pow_d(xi1, 1.0 / (s + 1));
     const double sinT = safe_sqrt(1.0 - cosT * cosT);
-    dir = to_global(mk(cx * out.x, cy * out.y, cz * out.z), mk(cp * sinT, sp * sinT, cosT));
+    const d3 axis = mk(cx * out.x, cy * out.y, cz * out.z);
+    dir = to_global(axis, mk(cp * sinT, sp * sinT, cosT));
+    // lafortune.h:99 normalizes C out before toGlobalShadingFrame normalizes it again: |C out|^2 = 0 or inf (C at the
+    // ends of its range) gives an infinite or zero vector first and NaN second, in every component
+    const double n2 = dot(axis, axis);
+    if (!(n2 > 0.0) || n2 > 1.7976931348623157e308) dir = mk(__builtin_nan(""), __builtin_nan(""), __builtin_nan(""));
     double rgb[3];
     eval_pdf(dir, out, component, rgb, pdf);
     flag = kFlagSpecular;
@@ -1231,8 +1236,8 @@ struct EpdNdf
   const float* tab;
   __device__ explicit EpdNdf(const double* q) : beta(q[0]), p(q[1])
   {
-    // compute_normalization (epd.h:160-178)
-    normalization = ((p > kEps) ? (p * kInvPi) * (1.0 / tgamma(1.0 / p)) : 0.0) / (beta * beta);
+    // compute_normalization (epd.h:160-178); p <= eps returns 0 before the division by beta^2 (0, not 0 / 0, at beta = 0)
+    normalization = (p > kEps) ? ((p * kInvPi) * (1.0 / tgamma(1.0 / p))) / (beta * beta) : 0.0;
     inv_p = 1.0 / p;
     tab = reinterpret_cast<const float*>(__builtin_bit_cast(unsigned long long, q[kTableSlot]));
   }
@@ -1277,7 +1282,9 @@ struct EpdNdf
     sincos(2.0 * kPi * xi0, &sp, &cp);
     // xi1 = 1: the reference's gamma_q_inv(a, q = 1) starts its Halley iteration at p = 0, x = 0, where
     // t = (P - p) / R(a, 0) = 0 / 0 (util/invgamma.h:404-414): its sampled normal is NaN, and so is this one
-    const double g = (xi1 >= 1.0) ? __builtin_nan("") : gamma_q_inv_d(inv_p, xi1);
+    // p = 0: a = 1 / p is infinite and the reference's initial estimate is inf - inf for every xi1 in (0, 1)
+    const bool undefined = (xi1 >= 1.0) || (inv_p > 1.7976931348623157e308 && xi1 > 0.0);
+    const double g = undefined ? __builtin_nan("") : gamma_q_inv_d(inv_p, xi1);
     const double tan2 = beta * beta * pow_d(g, inv_p);
     const double cosT = 1.0 / sqrt(1.0 + tan2);
     const double sinT = safe_sqrt(1.0 - cosT * cosT);

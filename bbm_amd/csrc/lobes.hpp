@@ -234,7 +234,12 @@ struct Lafortune
     sincosf_glibc(xi0 * kPi2F, &sp, &cp);
     const float cosT = float(pow(double(xi1), 1.0 / (s + 1)));
     const float sinT = float(safe_sqrt(1.0 - cosT * cosT));
-    dir = to_global(mk3(cx * out.x, cy * out.y, cz * out.z), mk3(cp * sinT, sp * sinT, cosT));
+    const v3 axis = mk3(cx * out.x, cy * out.y, cz * out.z);
+    dir = to_global(axis, mk3(cp * sinT, sp * sinT, cosT));
+    // lafortune.h:99 normalizes C out before toGlobalShadingFrame normalizes it again: |C out|^2 = 0 or inf (C at the
+    // ends of its range) gives an infinite or zero vector first and NaN second, in every component
+    const float n2 = dot3(axis, axis);
+    if (!(n2 > 0.0f) || n2 > 3.40282347e38f) dir = mk3(__builtin_nanf(""), __builtin_nanf(""), __builtin_nanf(""));
     float rgb[3];
     eval_pdf<kModePdf>(dir, out, component, rgb, pdf);
     flag = kFlagSpecular;

@@ -410,6 +410,7 @@ constexpr bool kLowExactDefault = true;
 #else
 constexpr bool kLowExactDefault = false;
 #endif
+constexpr float kLowFastMaxC = 16.0f;
 
 // ndf::low (include/ndf/low.h:32-141): the unnormalised ABC "S" term of [Low 2012] as an NDF.
 // eval pow(1 + B (1 - z), -C) in double; pdf = eval B (1/(2 pi)) normalization with the
@@ -435,9 +436,12 @@ struct LowNdf
   __device__ __forceinline__ float eval(v3 h) const
   {
     // pow(1 + B (1 - z), -C) in double in the reference; powf_fast: within ~1e-6; EXACT (exact mode): the double
-    // power (f64::pow_d) of the double base, rounded to float
+    // power (f64::pow_d) of the double base, rounded to float.  The float base is 1.2e-7 off the double one and the
+    // power multiplies that by C (C = 1e6: S was 6 % off, tests/test_gpu_edge_params.py), so the fast power is kept
+    // to C <= kLowFastMaxC, where that stays below 2e-6; a larger C takes the double power in every mode.
     float S;
-    if constexpr (EXACT || kLowExactDefault) S = float(f64::pow_d(1.0 + double(B) * (1.0 - double(h.z)), -double(C)));
+    if (EXACT || kLowExactDefault || !(C <= kLowFastMaxC))
+      S = float(f64::pow_d(1.0 + double(B) * (1.0 - double(h.z)), -double(C)));
     else S = powf_fast(float(1.0 + B * (1.0 - h.z)), -C);
     return (h.z > 0) ? S : 0.0f;
   }
