@@ -195,6 +195,9 @@ __device__ __forceinline__ void st4(float* p, uint64_t t, float a, float b, floa
 // the compiler's choice.  Raised per model where a VALU-bound evaluation would otherwise hold two or three waves
 // per SIMD (too few to hide the f64 / transcendental latencies).
 template<class Model> struct eval_waves { static constexpr int value = 1; };
+// The same floor for k_eval_pdf_v4 alone (the uniform-parameter quad kernel); by default the model's eval_waves.  A
+// floor set here reaches neither the per-lane and world-space kernels nor an aggregate over the model.
+template<class Model> struct eval_v4_waves { static constexpr int value = eval_waves<Model>::value; };
 
 // Whether k_eval_pdf_v4 issues a thread's first quad of loads before the LDS table prologue and the model's
 // construction (their latencies then overlap; the loaded registers stay live across both).  Measured (ms, 100 M /
@@ -224,7 +227,7 @@ template<class Model> struct eval_pipeline { static constexpr bool value = false
 template<class Model> struct eval_grid_cap { static constexpr uint64_t value = 0; };
 
 template<class Model, int MODE, bool MASK, bool NT, bool EXACT = false>
-__global__ __launch_bounds__(kBlock) BBM_HIP_KERNEL_ATTR __attribute__((amdgpu_waves_per_eu(eval_waves<Model>::value, 8)))
+__global__ __launch_bounds__(kBlock) BBM_HIP_KERNEL_ATTR __attribute__((amdgpu_waves_per_eu(eval_v4_waves<Model>::value, 8)))
 void k_eval_pdf_v4(EvalArgs a)
 {
   const uint64_t n4 = a.n >> 2;

@@ -195,6 +195,22 @@ __device__ __forceinline__ float sqrt_nr(float x)
 #endif
 }
 
+// sqrt_nr for an argument that is provably never subnormal and never -inf: what is left outside the normal range is
+// +-0, +inf or NaN, each of which is its own root (the hardware root returns exactly these: sqrt(-0) = -0, a quiet
+// NaN operand comes back as it is), so the argument itself stands in for v_sqrt_f32 -- a quarter-rate instruction
+// that the select otherwise executes on every lane.  Same float as sqrt_nr on that domain.
+__device__ __forceinline__ float sqrt_nr_ns(float x)
+{
+#if defined(BBM_HIP_SQRT_IEEE) || defined(BBM_HIP_NO_SQRT_NS)
+  return sqrt_nr(x);       // A/B: the hardware-root fallback
+#else
+  const float y = __builtin_amdgcn_rsqf(x);
+  const float s = x * y;
+  const float s1 = __builtin_fmaf(__builtin_fmaf(-s, s, x), 0.5f * y, s);
+  return __builtin_isnormal(x) ? s1 : x;
+#endif
+}
+
 // ---------------------------------------------------------------- exponentials and powers
 //
 // Measured on gfx950 (tools/hwmath_probe.hip, every float in range): v_log_f32 is within 2.0 * 2^-24 relative of
@@ -969,6 +985,20 @@ __device__ __forceinline__ float f_div_d(double n, double d)
   return __builtin_isfinite(q) ? float(q) : float(n) * r;   // d = 0 / inf, n = inf: IEEE result
 }
 
+// f_div_d where the quotient is finite on every lane whose result is used (finite n, a finite d bounded away from
+// 0 whose float is finite too): the remainder step alone, without the special-case select.  Same float as f_div_d
+// there; on the other lanes (selected away by the caller) it is NaN where f_div_d returned the IEEE inf / NaN.
+__device__ __forceinline__ float f_div_d_fin(double n, double d)
+{
+#ifdef BBM_HIP_NO_FDIV_FIN
+  return f_div_d(n, d);    // A/B
+#else
+  const float r = __builtin_amdgcn_rcpf(float(d));
+  const double q0 = double(float(n) * r);
+  return float(__builtin_fma(__builtin_fma(-d, q0, n), double(r), q0));
+#endif
+}
+
 // ---------------------------------------------------------------- compensated f32 (double-float)
 //
 // Where the reference promotes to double only to form a product of two floats and divide it
@@ -1003,6 +1033,32 @@ __device__ __forceinline__ float div_ff(float nh, float nl, float dh, float dl)
   return res;
 #else
   return __builtin_isnormal(q1) ? q1 : nh * r;     // subnormal / special results: see div_nr
+#endif
+}
+
+// div_ff(nh, nl, dh, 0): a one-float divisor, one FMA less.  div_ff's fma(-q, dl, nl) with dl = 0 is a sum of a
+// zero and nl, which the compiler cannot fold (q may be infinite), but the result is the same float for every operand:
+//  * q finite, nl != 0: the sum is nl exactly.
+//  * q finite, nl = +-0: the sum is a zero whose sign may differ from nl's.  Added to the remainder e it changes
+//    nothing unless e = 0 too; then rem is a zero of either sign and q1 = fma(+-0, r, q) is q for q != 0, and a zero
+//    (or NaN, r infinite) for q = +-0 -- not a normal float, so the select returns nh * r in both forms.
+//  * q infinite or NaN: div_ff's rem is NaN; here rem and q1 are infinite or NaN.  Either way q1 is not a normal
+//    float and the select returns nh * r.
+__device__ __forceinline__ float div_ff_d1(float nh, float nl, float dh)
+{
+#ifdef BBM_HIP_NO_DIV_FF_D1
+  return div_ff(nh, nl, dh, 0.0f);    // A/B
+#else
+  const float r = __builtin_amdgcn_rcpf(dh);
+  float q = nh * r;
+  q = __builtin_fmaf(__builtin_fmaf(-dh, q, nh), r, q);
+  const float rem = __builtin_fmaf(-dh, q, nh) + nl;
+  const float q1 = __builtin_fmaf(rem, r, q);
+#ifdef BBM_HIP_DIV_SUB
+  return div_ff(nh, nl, dh, 0.0f);
+#else
+  return __builtin_isnormal(q1) ? q1 : nh * r;
+#endif
 #endif
 }
 
@@ -1049,7 +1105,10 @@ __device__ __forceinline__ double safe_sqrt(double a) { return sqrt((a < 0.0) ? 
 // core/spherical.h:79-80 sinTheta2 = bbm::max(1 - z*z, 0) -> fmaxf (result_t<float,int> = float)
 __device__ __forceinline__ float sin_theta2(v3 v) { return fmaxf(1 - v.z * v.z, 0.0f); }
 // spherical.h:179-180 tanTheta = sinTheta / cosTheta; :185-186 tanTheta2 = sinTheta2 / cosTheta2
-__device__ __forceinline__ float tan_theta(v3 v) { return div_nr(sqrt_nr(sin_theta2(v)), v.z); }
+// sinTheta2 is +0 or in [2^-24, 1] for EVERY float z, so its root needs no hardware-root fallback (sqrt_nr_ns):
+// z^2 rounds to a float >= 0 (or NaN); in [1/2, 2] the difference 1 - z^2 is exact (Sterbenz), a multiple of 2^-24;
+// below 1/2 it exceeds 1/2; above 1 it is negative and NaN stays NaN, both of which fmaxf turns into +0.
+__device__ __forceinline__ float tan_theta(v3 v) { return div_nr(sqrt_nr_ns(sin_theta2(v)), v.z); }
 __device__ __forceinline__ float tan_theta2(v3 v) { return div_nr(sin_theta2(v), v.z * v.z); }
 
 // std::clamp(a, T(lo), T(hi)) (backbone/native/include/backbone/math.h:106-107)

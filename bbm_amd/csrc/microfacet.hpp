@@ -65,7 +65,13 @@ struct Beckmann
     if (Aniso) a = div_nr(1.0f, sqrtf(div_nr(sqnorm2(v.x * au, v.y * av), pow2f(v.z))));
     else a = div_nr(1.0f, au * tan_theta(v));
     const double ad = a;
-    const float g = f_div_d(3.535 * ad + 2.181 * ad * ad, 1 + 2.276 * ad + 2.577 * ad * ad);
+    // g is used where a < 1.6 only.  For a roughness in its box (alpha > 0) a = 1 / (alpha tan) is >= 0 there, the
+    // numerator is a finite double and the denominator 1 + 2.276 a + 2.577 a^2 lies in [1, 11.3]: its float is finite
+    // and nonzero and so is the quotient -- f_div_d's special-case select never fires on a lane whose g is used
+    // (f_div_d_fin).  a = NaN, +inf and a >= 1.6 select 1.  Outside the box (alpha < 0, which nothing rejects) the
+    // same holds while |alpha tan| >= 2^-60 (the denominator has no real root, 2.276^2 < 4 x 2.577, and stays in
+    // [0.497, 2^122]); closer to zero the denominator's float overflows and both forms return NaN.
+    const float g = f_div_d_fin(3.535 * ad + 2.181 * ad * ad, 1 + 2.276 * ad + 2.577 * ad * ad);
     return mask ? ((a < 1.6) ? g : 1.0f) : 0.0f;
   }
 
@@ -370,10 +376,19 @@ struct VGroove
     float pih, pil, poh, pol;
     two_prod(tm, in.z, pih, pil);
     two_prod(tm, out.z, poh, pol);
-    const bool li = (pih < inm) || (pih == inm && pil < 0.0f);
+    // The conditions are combined with | and &, not || and &&: every operand is a plain comparison, and the
+    // short-circuit forms compiled to two exec-mask regions per pair, which cut the kernel's unrolled body into
+    // separate basic blocks -- the scheduler then could not interleave the four pairs as eval_pdf intends.
+#ifdef BBM_HIP_VGROOVE_SHORT_CIRCUIT
+    const bool li = (pih < inm) || (pih == inm && pil < 0.0f);     // A/B: the earlier form
     const bool lo = (poh < outm) || (poh == outm && pol < 0.0f);
     const bool use_i = li && (!lo || pih * outm <= poh * inm);
-    const float g = div_ff(use_i ? pih : poh, use_i ? pil : pol, use_i ? inm : outm, 0.0f);
+#else
+    const bool li = bool(int(pih < inm) | (int(pih == inm) & int(pil < 0.0f)));
+    const bool lo = bool(int(poh < outm) | (int(poh == outm) & int(pol < 0.0f)));
+    const bool use_i = bool(int(li) & (int(!lo) | int(pih * outm <= poh * inm)));
+#endif
+    const float g = div_ff_d1(use_i ? pih : poh, use_i ? pil : pol, use_i ? inm : outm);
     return ((inm > 0) && (outm > 0)) ? ((li || lo) ? g : 1.0f) : 0.0f;
   }
 };
@@ -478,7 +493,11 @@ struct FresnelCook
   __device__ explicit FresnelCook(const float* p) : eta(p[0]) {}
   __device__ __forceinline__ float eval(float c) const
   {
-    const float g = safe_sqrtf(eta * eta + c * c - 1.0f);
+    // the clamped radicand is never subnormal, for any eta and c: s = eta^2 + c^2 is a float >= 0 (or inf / NaN);
+    // for s in [1/2, 2] the difference s - 1 is exact (Sterbenz), so 0 or at least 2^-24 in magnitude; for s > 2 it
+    // is >= 1; for s < 1/2 it is negative and clamped to 0 -- the root needs no hardware fallback (sqrt_nr_ns)
+    const float g2 = eta * eta + c * c - 1.0f;
+    const float g = sqrt_nr_ns((g2 < 0.0f) ? 0.0f : g2);        // safe_sqrtf
     // c = (in.h + out.h) / 2 in (0, 1] where the result is used and g >= 0, for ANY eta (the attribute's bound
     // eta >= 1, bsdf_attribute.h:89, is metadata the reference does not enforce): g + c >= c is a positive normal
     // float, and c (g - c) + 1 is either 0 (only at eta = 0 with c = 1, where the numerator is 0 as well: NaN in

@@ -78,6 +78,16 @@ using CookTorranceM = Microfacet<Beckmann<false, false>, VGroove, FresnelCook, N
 #ifdef BBM_HIP_CT_WAVES
 template<> struct eval_waves<CookTorranceM> { static constexpr int value = BBM_HIP_CT_WAVES; };   // A/B
 #endif
+// With VGroove's conditions straight-line (microfacet.hpp) the four unrolled pairs of k_eval_pdf_v4 are one basic
+// block, and the scheduler, left to itself, interleaves them up to 106 VGPRs = 4 waves per SIMD (it was 91 = 5 with
+// the body cut into nine blocks).  A floor of 5 waves makes it schedule for registers instead: 66 VGPRs, 7 waves,
+// no scratch, in both the default and the exact-mode instantiation (-Rpass-analysis=kernel-resource-usage).  The
+// floor is for that kernel only (eval_v4_waves): under it the world-space and per-lane kernels of
+// Aggregate<Lambertian, CookTorrance> spilled 12-88 B per lane, so they and every other kernel keep eval_waves.
+#ifndef BBM_HIP_CT_V4_WAVES
+#define BBM_HIP_CT_V4_WAVES 5
+#endif
+template<> struct eval_v4_waves<CookTorranceM> { static constexpr int value = BBM_HIP_CT_V4_WAVES; };
 using GGXM = Microfacet<GGX<false>, Uncorrelated, FresnelCook, Norm::Walter, true>;                        // bsdfmodel/ggx.h:27-33
 using CookTorranceWalterM = Microfacet<Beckmann<false, true>, Uncorrelated, FresnelCook, Norm::Walter, true>;  // bsdfmodel/cooktorrancewalter.h:32-38
 
