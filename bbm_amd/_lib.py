@@ -76,6 +76,15 @@ SIGNATURES = {
     "bbm_hip_set_plan_geometry": (_I, [_P, _P]),
     "bbm_hip_set_eval_pdf": (_I, [_P, _I] + [_P] * 10 + [_SZ, _U32, _U32] + [_P] * 6),
     "bbm_hip_set_sample_eval": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _SZ, _U32, _U32] + [_P] * 12),
+    "bbm_hip_model_anisotropic": (_I, [_I]),
+    "bbm_hip_frame_to_local_tangent": (_I, [_P] * 10 + [_SZ, _P, _P, _P, _P]),
+    "bbm_hip_frame_to_global_tangent": (_I, [_P] * 10 + [_SZ, _P, _P, _P, _P]),
+    "bbm_hip_sample_eval_world_tangent": (_I, [_I, _P, _I] + [_P] * 12 + [_SZ, _U32, _U32] + [_P] * 12),
+    "bbm_hip_sample_eval_table_world_tangent": (_I, [_P, _I, _P] + [_P] * 12 + [_SZ, _U32, _U32] + [_P] * 12),
+    "bbm_hip_eval_pdf_world_tangent": (_I, [_I, _P, _I] + [_P] * 13 + [_SZ, _U32, _U32] + [_P] * 6),
+    "bbm_hip_eval_pdf_table_world_tangent": (_I, [_P, _I, _P] + [_P] * 13 + [_SZ, _U32, _U32] + [_P] * 6),
+    "bbm_hip_set_eval_pdf_tangent": (_I, [_P, _I] + [_P] * 13 + [_SZ, _U32, _U32] + [_P] * 6),
+    "bbm_hip_set_sample_eval_tangent": (_I, [_P, _I] + [_P] * 12 + [_SZ, _U32, _U32] + [_P] * 12),
     "bbm_hip_model_has_f64": (_I, [_I]),
     "bbm_hip_eval_pdf_f64": (_I, [_I, _P, _I, _P, _P, _P, _P, _P, _P, _P, _SZ, _U32, _U32, _P, _P, _P, _P, _P]),
     "bbm_hip_sample_f64": (_I, [_I, _P, _I, _P, _P, _P, _P, _P, _P, _SZ, _U32, _U32, _P, _P, _P, _P, _P, _P]),

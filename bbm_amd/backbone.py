@@ -181,17 +181,37 @@ def _normal_rows(normal, like, what="normal"):
     return normal[0].data_ptr(), normal[1].data_ptr(), normal[2].data_ptr()
 
 
-def _world_normal(normal, cosine, varying, in_, out):
-    """The world-space keywords of eval_pdf, checked ahead of every other argument: the normals' row pointers, or None
-    for the local call.  cosine needs a normal; normal= excludes varying= and float64 directions."""
+def _frame_rows(normal, tangent, like):
+    """normal= and tangent= of a world-space call, checked before anything else is (the tangent right after the
+    normal, by the same code): None for the local call, the normal's three row pointers, or those and the tangent's
+    three.  A tangent needs a normal: it fills the X and Y of the normal's frame."""
     if normal is None:
+        if tangent is not None:
+            raise ValueError("tangent= needs normal=: the tangent fills X and Y of the shading normal's frame")
+        return None
+    nptr = _normal_rows(normal, like)
+    return nptr if tangent is None else nptr + _normal_rows(tangent, like, what="tangent")
+
+
+def _frame_fn(name, fptr):
+    """The C-ABI call `name` for the frame pointers of _frame_rows: its *_tangent form where they hold a tangent."""
+    return getattr(_lib.load(), name + "_tangent" if fptr is not None and len(fptr) == 6 else name)
+
+
+def _world_normal(normal, cosine, varying, in_, out, tangent=None):
+    """The world-space keywords of eval_pdf, checked ahead of every other argument: the frame's row pointers
+    (_frame_rows), or None for the local call.  cosine and tangent need a normal; normal= excludes varying= and float64
+    directions."""
+    if normal is None:
+        if tangent is not None:
+            _frame_rows(normal, tangent, in_)
         if cosine:
             raise ValueError("cosine=True needs normal=: the cosine is that of `in` against the shading normal")
         return None
     if varying is not None:
         raise ValueError("normal= with varying=: there is no world-space call over per-lane parameters; "
                          "take the directions through to_local(normal, .) and use the local call")
-    nptr = _normal_rows(normal, in_)
+    nptr = _frame_rows(normal, tangent, in_)
     if _is_f64(in_) or _is_f64(out):
         raise TypeError("normal: the world-space calls are floatRGB only (float32 directions)")
     return nptr
@@ -202,30 +222,33 @@ def _with_cosine(result, k, cosine):
     return (result[k], result[-1]) if cosine else result[k]
 
 
-def _frame_call(fn_name, normal, v, mask, stream):
+def _frame_call(fn_name, normal, v, mask, stream, tangent=None):
     torch = _torch()
-    nptr = _normal_rows(normal, v)
+    nptr = _frame_rows(normal, tangent, v)
     if _is_f64(v):
         raise TypeError("shading frames: floatRGB only (float32 tensors)")
     x, y, z, n = _soa(v, what="v")
     mptr, _keep = _mask_ptr(mask, n)
     r = torch.empty((3, n), dtype=torch.float32, device=_device(v))
     _on_stream(stream, _keep, r)
-    _lib.check(getattr(_lib.load(), fn_name)(*nptr, x, y, z, mptr, n, r[0].data_ptr(), r[1].data_ptr(),
+    _lib.check(_frame_fn(fn_name, nptr)(*nptr, x, y, z, mptr, n, r[0].data_ptr(), r[1].data_ptr(),
                                               r[2].data_ptr(), _stream_ptr(stream)))
     return r
 
 
-def to_local(normal, v, mask=None, *, stream=None):
+def to_local(normal, v, mask=None, *, stream=None, tangent=None):
     """World-space vectors v (3, N) in the shading frame of one normal per lane (bbm_hip_frame_to_local): the
     reference's toLocalShadingFrame, transpose(toGlobalShadingFrame(normal)) v.  normal: (3, N) float32, any length
-    per normal; a lane whose normal is (about) zero, and a lane with mask == 0, gets (0, 0, 0).  -> (3, N)."""
-    return _frame_call("bbm_hip_frame_to_local", normal, v, mask, stream)
+    per normal; a lane whose normal is (about) zero, and a lane with mask == 0, gets (0, 0, 0).  -> (3, N).
+    tangent: (3, N) float32 world-space tangents, any length (bbm_hip_frame_to_local_tangent): X is the tangent's part
+    perpendicular to the normal, normalized, and Y = Z x X; a lane whose tangent has no such part (zero, parallel to the
+    normal, NaN) keeps the normal-only frame."""
+    return _frame_call("bbm_hip_frame_to_local", normal, v, mask, stream, tangent)
 
 
-def to_global(normal, v, mask=None, *, stream=None):
+def to_global(normal, v, mask=None, *, stream=None, tangent=None):
     """Local vectors v (3, N) in world space (bbm_hip_frame_to_global): toGlobalShadingFrame(normal) v; see to_local."""
-    return _frame_call("bbm_hip_frame_to_global", normal, v, mask, stream)
+    return _frame_call("bbm_hip_frame_to_global", normal, v, mask, stream, tangent)
 
 
 def _device(t):
@@ -453,6 +476,12 @@ class BsdfModel:
         eval / pdf / eval_pdf / sample / reflectance."""
         return _lib.check(_lib.load().bbm_hip_model_has_varying(self.model_id)) == 1
 
+    @property
+    def anisotropic(self):
+        """Whether the model's parameters run along the shading frame's X and Y (bbm_hip_model_anisotropic): the
+        models for which tangent= of the world-space calls turns the lobe."""
+        return bool(_lib.check(_lib.load().bbm_hip_model_anisotropic(self.model_id)))
+
     def has_table(self):
         """True if the model can be held in a MaterialTable (bbm_hip_model_has_table)."""
         return _lib.check(_lib.load().bbm_hip_model_has_table(self.model_id)) == 1
@@ -525,15 +554,18 @@ class BsdfModel:
 
     def eval_pdf(self, in_, out, component=bsdf_flag.All, unit=unit_t.Radiance, mask=None, *,
                  rgb=None, pdf=None, stream=None, mode=3, params64=None, exact=None, varying=None, normal=None,
-                 cosine=False):
+                 cosine=False, tangent=None):
         """varying: per-lane parameters, {attribute name or parameter index: float32 CUDA rows} (_varying); lane i
         then evaluates the model with those parameters replaced by row[i] (bbm_hip_eval_pdf_varying).
         normal: a (3, N) float32 tensor of shading normals selects the world-space call (bbm_hip_eval_pdf_world):
         `in_` and `out` are in world space, and the result is what to_local(normal, in_), to_local(normal, out) and
         this call give in sequence, in one launch.  cosine=True (with normal=): the result gains a last element, the
-        (N,) cosine of `in_` against the normal (the z of to_local(normal, in_)).  floatRGB only, not with varying=."""
+        (N,) cosine of `in_` against the normal (the z of to_local(normal, in_)).  floatRGB only, not with varying=.
+        tangent (with normal=): a (3, N) float32 tensor of world-space tangents, any length; for an anisotropic model
+        (self.anisotropic) the frame's X follows it (bbm_hip_eval_pdf_world_tangent; to_local's tangent=), so the x / y
+        roughness runs along the surface's own direction.  Any other model ignores it."""
         torch = _torch()
-        nptr = _world_normal(normal, cosine, varying, in_, out)
+        nptr = _world_normal(normal, cosine, varying, in_, out, tangent)
         if varying is not None and _is_f64(in_):
             raise TypeError("varying: per-lane parameters are floatRGB only (float32 tensors)")
         if _is_f64(in_):
@@ -552,7 +584,7 @@ class BsdfModel:
         if nptr is not None:
             cos = torch.empty((n,), dtype=torch.float32, device=dev) if cosine else None
             _on_stream(stream, cos)
-            _lib.check(lib.bbm_hip_eval_pdf_world(
+            _lib.check(_frame_fn("bbm_hip_eval_pdf_world", nptr)(
                 mid, self._pptr(), self._params.size, *nptr, ix, iy, iz, ox, oy, oz, mptr, n, int(component), int(unit),
                 *_eval_pdf_ptrs(mode, rgb, pdf), None if cos is None else cos.data_ptr(), s))
             return (rgb, pdf, cos) if cosine else (rgb, pdf)
@@ -619,7 +651,7 @@ class BsdfModel:
         return BsdfSample(d, p, f)
 
     def sample_eval(self, out, xi, component=bsdf_flag.All, unit=unit_t.Radiance, mask=None, *, value=True,
-                    weight=True, stream=None, exact=None, normal=None):
+                    weight=True, stream=None, exact=None, normal=None, tangent=None):
         """One BSDF call per bounce in one launch (bbm_hip_sample_eval): -> (BsdfSample, value, weight).  The sample is
         sample(out, xi)'s, value (3, N) is eval_pdf(sample.direction, out)[0] and weight (3, N) is
         value * direction_z / pdf where pdf > epsilon(float32), else 0 -- each bit for bit what the staged calls give,
@@ -627,15 +659,16 @@ class BsdfModel:
         stored and None is returned for it.  floatRGB only.
         normal: a (3, N) float32 tensor of shading normals selects the world-space call (bbm_hip_sample_eval_world):
         `out` and the returned direction are in world space, everything else is what to_local(normal, out), this call
-        and to_global(normal, direction) give in sequence (the weight's cosine is the local direction's)."""
-        nptr = None if normal is None else _normal_rows(normal, out)
+        and to_global(normal, direction) give in sequence (the weight's cosine is the local direction's).
+        tangent (with normal=): as eval_pdf's (bbm_hip_sample_eval_world_tangent)."""
+        nptr = _frame_rows(normal, tangent, out)
         ox, oy, oz, n, x0, x1 = _sample_eval_inputs(out, xi)
         mptr, _keep = _mask_ptr(mask, n)
         outs = _sample_eval_outputs(n, x0.device, value, weight)
         _on_stream(stream, _keep, *outs)
         d, p, f, v, w = outs
         lib = _lib.load()
-        fn, pre = (lib.bbm_hip_sample_eval, ()) if nptr is None else (lib.bbm_hip_sample_eval_world, nptr)
+        fn, pre = (lib.bbm_hip_sample_eval, ()) if nptr is None else (_frame_fn("bbm_hip_sample_eval_world", nptr), nptr)
         _lib.check(fn(
             self._call_id(exact), self._pptr(), self._params.size, *pre, ox, oy, oz, x0.data_ptr(), x1.data_ptr(), mptr, n,
             int(component), int(unit), d[0].data_ptr(), d[1].data_ptr(), d[2].data_ptr(), p.data_ptr(), f.data_ptr(),
@@ -919,12 +952,13 @@ class AggregateModel:
         return False
 
     def eval_pdf(self, in_, out, component=bsdf_flag.All, unit=unit_t.Radiance, mask=None, *,
-                 rgb=None, pdf=None, stream=None, mode=3, varying=None, normal=None, cosine=False):
-        """normal, cosine: BsdfModel.eval_pdf's, staged -- a tree has no fused kernel, so the directions go through
-        to_local(normal, .) and the cosine is the z of to_local(normal, in_)."""
-        if _world_normal(normal, cosine, varying, in_, out) is not None:
-            li = to_local(normal, in_, mask, stream=stream)
-            r = self.eval_pdf(li, to_local(normal, out, mask, stream=stream), component, unit, mask, rgb=rgb, pdf=pdf,
+                 rgb=None, pdf=None, stream=None, mode=3, varying=None, normal=None, cosine=False, tangent=None):
+        """normal, cosine, tangent: BsdfModel.eval_pdf's, staged -- a tree has no fused kernel, so the directions go
+        through to_local(normal, ., tangent=tangent) and the cosine is the z of to_local(normal, in_).  A tangent
+        always goes to the frame calls: a tree's children may be anisotropic."""
+        if _world_normal(normal, cosine, varying, in_, out, tangent) is not None:
+            li = to_local(normal, in_, mask, stream=stream, tangent=tangent)
+            r = self.eval_pdf(li, to_local(normal, out, mask, stream=stream, tangent=tangent), component, unit, mask, rgb=rgb, pdf=pdf,
                               stream=stream, mode=mode)
             return (*r, li[2]) if cosine else r
         self._no_varying(varying)
@@ -975,22 +1009,21 @@ class AggregateModel:
         return BsdfSample(d, p, f)
 
     def sample_eval(self, out, xi, component=bsdf_flag.All, unit=unit_t.Radiance, mask=None, *, value=True,
-                    weight=True, stream=None, exact=None, normal=None):
+                    weight=True, stream=None, exact=None, normal=None, tangent=None):
         """BsdfModel.sample_eval for a composed or runtime tree -- staged: a tree has no fused kernel, so this runs
         the tree's own sample and eval_pdf on the GPU (two launches, the direction goes through memory) and forms
         the weight with torch float32 ops under the same rule (value * direction_z / pdf where pdf > epsilon, else
         0).  -> (BsdfSample, value or None, weight or None).  floatRGB only; a tree has no exact mode of its own, so
         exact must be None.  normal: world space, staged as well -- to_local(normal, out), the above, then
-        to_global(normal, direction)."""
+        to_global(normal, direction), both with tangent= where one is given."""
         torch = _torch()
         if exact is not None:
             raise NotImplementedError("sample_eval: composed aggregates follow the process-wide mode (exact=None)")
-        if normal is not None:
-            _normal_rows(normal, out)
+        if _frame_rows(normal, tangent, out) is not None:
             _sample_eval_inputs(out, xi)
-            s, v, w = self.sample_eval(to_local(normal, out, mask, stream=stream), xi, component, unit, mask,
-                                       value=value, weight=weight, stream=stream)
-            return BsdfSample(to_global(normal, s.direction, mask, stream=stream), s.pdf, s.flag), v, w
+            s, v, w = self.sample_eval(to_local(normal, out, mask, stream=stream, tangent=tangent), xi, component, unit,
+                                       mask, value=value, weight=weight, stream=stream)
+            return BsdfSample(to_global(normal, s.direction, mask, stream=stream, tangent=tangent), s.pdf, s.flag), v, w
         _sample_eval_inputs(out, xi)
         s = self.sample(out, xi, component, unit, mask, stream=stream)
         if not (value or weight):
@@ -1151,9 +1184,9 @@ class MaterialTable:
         return material.data_ptr()
 
     def eval_pdf(self, in_, out, component=bsdf_flag.All, unit=unit_t.Radiance, mask=None, *, material,
-                 rgb=None, pdf=None, stream=None, mode=3, exact=None, normal=None, cosine=False):
-        """normal, cosine: as BsdfModel.eval_pdf's (bbm_hip_eval_pdf_table_world)."""
-        nptr = _world_normal(normal, cosine, None, in_, out)
+                 rgb=None, pdf=None, stream=None, mode=3, exact=None, normal=None, cosine=False, tangent=None):
+        """normal, cosine, tangent: as BsdfModel.eval_pdf's (bbm_hip_eval_pdf_table_world and its _tangent form)."""
+        nptr = _world_normal(normal, cosine, None, in_, out, tangent)
         if _is_f64(in_) or _is_f64(out):
             raise TypeError("MaterialTable: material tables are floatRGB only (float32 tensors)")
         h = self._live()
@@ -1167,7 +1200,7 @@ class MaterialTable:
         if nptr is not None:
             cos = _torch().empty((n,), dtype=_torch().float32, device=dev) if cosine else None
             _on_stream(stream, cos)
-            _lib.check(_lib.load().bbm_hip_eval_pdf_table_world(
+            _lib.check(_frame_fn("bbm_hip_eval_pdf_table_world", nptr)(
                 h, self._flags(exact), idx, *nptr, ix, iy, iz, ox, oy, oz, mptr, n, int(component), int(unit),
                 *_eval_pdf_ptrs(mode, rgb, pdf), None if cos is None else cos.data_ptr(), _stream_ptr(stream)))
             return (rgb, pdf, cos) if cosine else (rgb, pdf)
@@ -1201,11 +1234,11 @@ class MaterialTable:
         return BsdfSample(d, p, f)
 
     def sample_eval(self, out, xi, component=bsdf_flag.All, unit=unit_t.Radiance, mask=None, *, material,
-                    value=True, weight=True, stream=None, exact=None, normal=None):
+                    value=True, weight=True, stream=None, exact=None, normal=None, tangent=None):
         """BsdfModel.sample_eval with a material per lane (bbm_hip_sample_eval_table): lane i gets what the table's
-        sample followed by its eval_pdf at the sampled direction returns for material[i], and the weight.  normal:
-        as BsdfModel.sample_eval's (bbm_hip_sample_eval_table_world)."""
-        nptr = None if normal is None else _normal_rows(normal, out)
+        sample followed by its eval_pdf at the sampled direction returns for material[i], and the weight.  normal,
+        tangent: as BsdfModel.sample_eval's (bbm_hip_sample_eval_table_world and its _tangent form)."""
+        nptr = _frame_rows(normal, tangent, out)
         ox, oy, oz, n, x0, x1 = _sample_eval_inputs(out, xi)
         h = self._live()
         dev = x0.device
@@ -1215,7 +1248,8 @@ class MaterialTable:
         _on_stream(stream, _keep, material, *outs)
         d, p, f, v, w = outs
         lib = _lib.load()
-        fn, pre = (lib.bbm_hip_sample_eval_table, ()) if nptr is None else (lib.bbm_hip_sample_eval_table_world, nptr)
+        fn, pre = ((lib.bbm_hip_sample_eval_table, ()) if nptr is None else
+                   (_frame_fn("bbm_hip_sample_eval_table_world", nptr), nptr))
         _lib.check(fn(
             h, self._flags(exact), idx, *pre, ox, oy, oz, x0.data_ptr(), x1.data_ptr(), mptr, n, int(component), int(unit),
             d[0].data_ptr(), d[1].data_ptr(), d[2].data_ptr(), p.data_ptr(), f.data_ptr(), *_row_ptrs(v),
@@ -1400,8 +1434,10 @@ class MaterialSet:
         return plan, False
 
     def eval_pdf(self, in_, out, component=bsdf_flag.All, unit=unit_t.Radiance, mask=None, *, material=None,
-                 plan=None, rgb=None, pdf=None, stream=None, mode=3, exact=None, normal=None, cosine=False):
-        nptr = _world_normal(normal, cosine, None, in_, out)
+                 plan=None, rgb=None, pdf=None, stream=None, mode=3, exact=None, normal=None, cosine=False,
+                 tangent=None):
+        """tangent (with normal=): read by the rows whose model is anisotropic (bbm_hip_set_eval_pdf_tangent)."""
+        nptr = _world_normal(normal, cosine, None, in_, out, tangent)
         if _is_f64(in_) or _is_f64(out):
             raise TypeError("MaterialSet: material sets are floatRGB only (float32 tensors)")
         ix, iy, iz, n = _soa(in_, what="in")
@@ -1413,7 +1449,7 @@ class MaterialSet:
         _on_stream(stream, _keep, rgb, pdf, cos)
         p, own = self._planned(material, plan, stream, n, dev)
         try:
-            _lib.check(_lib.load().bbm_hip_set_eval_pdf(
+            _lib.check(_frame_fn("bbm_hip_set_eval_pdf", nptr)(
                 p._live(), MaterialTable._flags(exact), *(nptr or (None, None, None)), ix, iy, iz, ox, oy, oz, mptr, n,
                 int(component), int(unit), *_eval_pdf_ptrs(mode, rgb, pdf), None if cos is None else cos.data_ptr(),
                 _stream_ptr(stream)))
@@ -1429,8 +1465,8 @@ class MaterialSet:
         return _with_cosine(self.eval_pdf(in_, out, component, unit, mask, mode=2, **kw), 1, kw.get("cosine", False))
 
     def sample_eval(self, out, xi, component=bsdf_flag.All, unit=unit_t.Radiance, mask=None, *, material=None,
-                    plan=None, value=True, weight=True, stream=None, exact=None, normal=None):
-        nptr = None if normal is None else _normal_rows(normal, out)
+                    plan=None, value=True, weight=True, stream=None, exact=None, normal=None, tangent=None):
+        nptr = _frame_rows(normal, tangent, out)
         ox, oy, oz, n, x0, x1 = _sample_eval_inputs(out, xi)
         dev = x0.device
         mptr, _keep = _mask_ptr(mask, n)
@@ -1439,7 +1475,7 @@ class MaterialSet:
         d, p_, f, v, w = outs
         p, own = self._planned(material, plan, stream, n, dev)
         try:
-            _lib.check(_lib.load().bbm_hip_set_sample_eval(
+            _lib.check(_frame_fn("bbm_hip_set_sample_eval", nptr)(
                 p._live(), MaterialTable._flags(exact), *(nptr or (None, None, None)), ox, oy, oz, x0.data_ptr(),
                 x1.data_ptr(), mptr, n, int(component), int(unit), d[0].data_ptr(), d[1].data_ptr(), d[2].data_ptr(),
                 p_.data_ptr(), f.data_ptr(), *_row_ptrs(v), *_row_ptrs(w), _stream_ptr(stream)))

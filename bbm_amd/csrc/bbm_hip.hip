@@ -290,6 +290,15 @@ int sample_eval_args(const float* out_x, const float* out_y, const float* out_z,
   return BBM_HIP_OK;
 }
 
+// The tangent of the *_tangent calls: all three pointers (the tangent call), none (the call is its counterpart
+// without one); a mixture is an error, found before anything else is looked at.
+int tangent_arg(const float* tx, const float* ty, const float* tz, bool& tangent)
+{
+  tangent = tx && ty && tz;
+  if (!tangent && (tx || ty || tz)) return fail(BBM_HIP_ERR_INVALID_ARG, "tangent: give tx, ty and tz or none");
+  return BBM_HIP_OK;
+}
+
 int refl_args(const float* out_x, const float* out_y, const float* out_z, const uint8_t* mask, size_t n,
               uint32_t component, float* r, float* g, float* b, ReflArgs& a)
 {
@@ -381,9 +390,11 @@ int bbm_hip_sample(int model_id, const float* params, int nparams,
   return e->run.sample(a, static_cast<hipStream_t>(stream));
 }
 
-// world: the normal pointers are the call's (bbm_hip_sample_eval_world), else they are not looked at
+// world: the normal pointers are the call's (bbm_hip_sample_eval_world), else they are not looked at; the tangent
+// pointers (bbm_hip_sample_eval_world_tangent) are all set or all NULL, and read only by an anisotropic row
 static int sample_eval_common(bool world, int model_id, const float* params, int nparams,
                               const float* nx, const float* ny, const float* nz,
+                              const float* tx, const float* ty, const float* tz,
                               const float* out_x, const float* out_y, const float* out_z,
                               const float* xi0, const float* xi1,
                               const uint8_t* mask, size_t n, uint32_t component,
@@ -404,6 +415,13 @@ static int sample_eval_common(bool world, int model_id, const float* params, int
   a.s.p = tmp.p;
   if (!world) return e->run.sample_eval(a, static_cast<hipStream_t>(stream));
   a.nx = nx; a.ny = ny; a.nz = nz;
+  if (tx && e->tangent.sample_eval)
+  {
+    SampleEvalTangentArgs t;
+    static_cast<SampleEvalArgs&>(t) = a;
+    t.tx = tx; t.ty = ty; t.tz = tz;
+    return e->tangent.sample_eval(t, static_cast<hipStream_t>(stream));
+  }
   return e->run.sample_eval_world(a, static_cast<hipStream_t>(stream));
 }
 
@@ -415,8 +433,9 @@ int bbm_hip_sample_eval(int model_id, const float* params, int nparams,
                         float* r, float* g, float* b, float* wr, float* wg, float* wb, void* stream)
 {
   (void)unit;
-  return sample_eval_common(false, model_id, params, nparams, nullptr, nullptr, nullptr, out_x, out_y, out_z, xi0, xi1,
-                            mask, n, component, dir_x, dir_y, dir_z, pdf, flag, r, g, b, wr, wg, wb, stream);
+  return sample_eval_common(false, model_id, params, nparams, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+                            out_x, out_y, out_z, xi0, xi1, mask, n, component, dir_x, dir_y, dir_z, pdf, flag, r, g, b,
+                            wr, wg, wb, stream);
 }
 
 int bbm_hip_sample_eval_world(int model_id, const float* params, int nparams,
@@ -428,20 +447,37 @@ int bbm_hip_sample_eval_world(int model_id, const float* params, int nparams,
                               float* r, float* g, float* b, float* wr, float* wg, float* wb, void* stream)
 {
   (void)unit;
-  return sample_eval_common(true, model_id, params, nparams, nx, ny, nz, out_x, out_y, out_z, xi0, xi1,
-                            mask, n, component, dir_x, dir_y, dir_z, pdf, flag, r, g, b, wr, wg, wb, stream);
+  return sample_eval_common(true, model_id, params, nparams, nx, ny, nz, nullptr, nullptr, nullptr, out_x, out_y, out_z,
+                            xi0, xi1, mask, n, component, dir_x, dir_y, dir_z, pdf, flag, r, g, b, wr, wg, wb, stream);
+}
+
+int bbm_hip_sample_eval_world_tangent(int model_id, const float* params, int nparams,
+                                      const float* nx, const float* ny, const float* nz,
+                                      const float* tx, const float* ty, const float* tz,
+                                      const float* out_x, const float* out_y, const float* out_z,
+                                      const float* xi0, const float* xi1,
+                                      const uint8_t* mask, size_t n, uint32_t component, uint32_t unit,
+                                      float* dir_x, float* dir_y, float* dir_z, float* pdf, uint32_t* flag,
+                                      float* r, float* g, float* b, float* wr, float* wg, float* wb, void* stream)
+{
+  (void)unit;
+  bool tangent;
+  if (const int rc = tangent_arg(tx, ty, tz, tangent)) return rc;
+  return sample_eval_common(true, model_id, params, nparams, nx, ny, nz, tx, ty, tz, out_x, out_y, out_z,
+                            xi0, xi1, mask, n, component, dir_x, dir_y, dir_z, pdf, flag, r, g, b, wr, wg, wb, stream);
 }
 
 // eval / pdf / eval + pdf in world space (eval_world.hpp).  The mode is taken from the outputs that are not NULL, with
 // bbm_hip_eval_pdf_varying's checks (eval_args); the normal is required, the cosine optional.
-int bbm_hip_eval_pdf_world(int model_id, const float* params, int nparams,
-                           const float* nx, const float* ny, const float* nz,
-                           const float* in_x, const float* in_y, const float* in_z,
-                           const float* out_x, const float* out_y, const float* out_z,
-                           const uint8_t* mask, size_t n, uint32_t component, uint32_t unit,
-                           float* r, float* g, float* b, float* pdf, float* cos_in, void* stream)
+// tx, ty, tz: all set (bbm_hip_eval_pdf_world_tangent) or all NULL; read only by an anisotropic row
+static int eval_pdf_world_common(int model_id, const float* params, int nparams,
+                                 const float* nx, const float* ny, const float* nz,
+                                 const float* tx, const float* ty, const float* tz,
+                                 const float* in_x, const float* in_y, const float* in_z,
+                                 const float* out_x, const float* out_y, const float* out_z,
+                                 const uint8_t* mask, size_t n, uint32_t component,
+                                 float* r, float* g, float* b, float* pdf, float* cos_in, void* stream)
 {
-  (void)unit;
   const CallExactScope mode_scope(model_id);
   EvalArgs tmp;
   const ModelEntry* e;
@@ -454,13 +490,47 @@ int bbm_hip_eval_pdf_world(int model_id, const float* params, int nparams,
   if ((rc = eval_args(mode, in_x, in_y, in_z, out_x, out_y, out_z, mask, n, component, r, g, b, pdf, a.e))) return rc;
   a.e.p = tmp.p;
   a.nx = nx; a.ny = ny; a.nz = nz; a.cos = cos_in;
+  if (tx && e->tangent.eval_pdf)
+  {
+    EvalTangentArgs t;
+    static_cast<EvalWorldArgs&>(t) = a;
+    t.tx = tx; t.ty = ty; t.tz = tz;
+    return e->tangent.eval_pdf(t, mode, static_cast<hipStream_t>(stream));
+  }
   return e->run.eval_pdf_world(a, mode, static_cast<hipStream_t>(stream));
+}
+
+int bbm_hip_eval_pdf_world(int model_id, const float* params, int nparams,
+                           const float* nx, const float* ny, const float* nz,
+                           const float* in_x, const float* in_y, const float* in_z,
+                           const float* out_x, const float* out_y, const float* out_z,
+                           const uint8_t* mask, size_t n, uint32_t component, uint32_t unit,
+                           float* r, float* g, float* b, float* pdf, float* cos_in, void* stream)
+{
+  (void)unit;
+  return eval_pdf_world_common(model_id, params, nparams, nx, ny, nz, nullptr, nullptr, nullptr, in_x, in_y, in_z,
+                               out_x, out_y, out_z, mask, n, component, r, g, b, pdf, cos_in, stream);
+}
+
+int bbm_hip_eval_pdf_world_tangent(int model_id, const float* params, int nparams,
+                                   const float* nx, const float* ny, const float* nz,
+                                   const float* tx, const float* ty, const float* tz,
+                                   const float* in_x, const float* in_y, const float* in_z,
+                                   const float* out_x, const float* out_y, const float* out_z,
+                                   const uint8_t* mask, size_t n, uint32_t component, uint32_t unit,
+                                   float* r, float* g, float* b, float* pdf, float* cos_in, void* stream)
+{
+  (void)unit;
+  bool tangent;
+  if (const int rc = tangent_arg(tx, ty, tz, tangent)) return rc;
+  return eval_pdf_world_common(model_id, params, nparams, nx, ny, nz, tx, ty, tz, in_x, in_y, in_z,
+                               out_x, out_y, out_z, mask, n, component, r, g, b, pdf, cos_in, stream);
 }
 
 // ------------------------------------------------------------------------------- shading frames (frame.hpp)
 
 static int frame_common(bool to_local, const float* nx, const float* ny, const float* nz,
-                        const float* x, const float* y, const float* z, const uint8_t* mask, size_t n,
+                        const float* tx, const float* ty, const float* tz, const float* x, const float* y, const float* z, const uint8_t* mask, size_t n,
                         float* rx, float* ry, float* rz, void* stream)
 {
   if (n == 0) return BBM_HIP_OK;
@@ -469,21 +539,45 @@ static int frame_common(bool to_local, const float* nx, const float* ny, const f
       (rc = check_dirs(rx, ry, rz, "output")))
     return rc;
   const FrameArgs a{nx, ny, nz, x, y, z, mask, n, rx, ry, rz};
-  return frame_launch(a, to_local, static_cast<hipStream_t>(stream));
+  if (!tx) return frame_launch(a, to_local, static_cast<hipStream_t>(stream));
+  FrameTangentArgs t;
+  static_cast<FrameArgs&>(t) = a;
+  t.tx = tx; t.ty = ty; t.tz = tz;
+  return frame_launch(t, to_local, static_cast<hipStream_t>(stream));
 }
 
 int bbm_hip_frame_to_local(const float* nx, const float* ny, const float* nz,
                            const float* x, const float* y, const float* z, const uint8_t* mask, size_t n,
                            float* lx, float* ly, float* lz, void* stream)
 {
-  return frame_common(true, nx, ny, nz, x, y, z, mask, n, lx, ly, lz, stream);
+  return frame_common(true, nx, ny, nz, nullptr, nullptr, nullptr, x, y, z, mask, n, lx, ly, lz, stream);
 }
 
 int bbm_hip_frame_to_global(const float* nx, const float* ny, const float* nz,
                             const float* lx, const float* ly, const float* lz, const uint8_t* mask, size_t n,
                             float* x, float* y, float* z, void* stream)
 {
-  return frame_common(false, nx, ny, nz, lx, ly, lz, mask, n, x, y, z, stream);
+  return frame_common(false, nx, ny, nz, nullptr, nullptr, nullptr, lx, ly, lz, mask, n, x, y, z, stream);
+}
+
+int bbm_hip_frame_to_local_tangent(const float* nx, const float* ny, const float* nz,
+                                   const float* tx, const float* ty, const float* tz,
+                                   const float* x, const float* y, const float* z, const uint8_t* mask, size_t n,
+                                   float* lx, float* ly, float* lz, void* stream)
+{
+  bool tangent;
+  if (const int rc = tangent_arg(tx, ty, tz, tangent)) return rc;
+  return frame_common(true, nx, ny, nz, tx, ty, tz, x, y, z, mask, n, lx, ly, lz, stream);
+}
+
+int bbm_hip_frame_to_global_tangent(const float* nx, const float* ny, const float* nz,
+                                    const float* tx, const float* ty, const float* tz,
+                                    const float* lx, const float* ly, const float* lz, const uint8_t* mask, size_t n,
+                                    float* x, float* y, float* z, void* stream)
+{
+  bool tangent;
+  if (const int rc = tangent_arg(tx, ty, tz, tangent)) return rc;
+  return frame_common(false, nx, ny, nz, tx, ty, tz, lx, ly, lz, mask, n, x, y, z, stream);
 }
 
 int bbm_hip_reflectance(int model_id, const float* params, int nparams,
@@ -714,14 +808,14 @@ int bbm_hip_eval_pdf_table(const bbm_hip_table* t, int call_flags, const uint32_
   return t->e->run.eval_pdf_tab(a, mode, static_cast<hipStream_t>(stream));
 }
 
-int bbm_hip_eval_pdf_table_world(const bbm_hip_table* t, int call_flags, const uint32_t* material,
-                                 const float* nx, const float* ny, const float* nz,
-                                 const float* in_x, const float* in_y, const float* in_z,
-                                 const float* out_x, const float* out_y, const float* out_z,
-                                 const uint8_t* mask, size_t n, uint32_t component, uint32_t unit,
-                                 float* r, float* g, float* b, float* pdf, float* cos_in, void* stream)
+static int eval_pdf_table_world_common(const bbm_hip_table* t, int call_flags, const uint32_t* material,
+                                       const float* nx, const float* ny, const float* nz,
+                                       const float* tx, const float* ty, const float* tz,
+                                       const float* in_x, const float* in_y, const float* in_z,
+                                       const float* out_x, const float* out_y, const float* out_z,
+                                       const uint8_t* mask, size_t n, uint32_t component,
+                                       float* r, float* g, float* b, float* pdf, float* cos_in, void* stream)
 {
-  (void)unit;
   int rc = table_call(t, call_flags, n, material);
   if (rc) return rc;
   if (!t->e->run.eval_pdf_tab_world)
@@ -736,7 +830,42 @@ int bbm_hip_eval_pdf_table_world(const bbm_hip_table* t, int call_flags, const u
   a.e.e.p = (mode & kModePdf) ? t->first_prepared : t->first_raw;
   a.e.nx = nx; a.e.ny = ny; a.e.nz = nz; a.e.cos = cos_in;
   a.src = {(mode & kModePdf) ? t->prepared : t->raw, material, t->count};
+  if (tx && t->e->tangent.eval_pdf_tab)
+  {
+    EvalTabTangentArgs ta;
+    static_cast<EvalWorldArgs&>(ta.e) = a.e;
+    ta.e.tx = tx; ta.e.ty = ty; ta.e.tz = tz;
+    ta.src = a.src;
+    return t->e->tangent.eval_pdf_tab(ta, mode, static_cast<hipStream_t>(stream));
+  }
   return t->e->run.eval_pdf_tab_world(a, mode, static_cast<hipStream_t>(stream));
+}
+
+int bbm_hip_eval_pdf_table_world(const bbm_hip_table* t, int call_flags, const uint32_t* material,
+                                 const float* nx, const float* ny, const float* nz,
+                                 const float* in_x, const float* in_y, const float* in_z,
+                                 const float* out_x, const float* out_y, const float* out_z,
+                                 const uint8_t* mask, size_t n, uint32_t component, uint32_t unit,
+                                 float* r, float* g, float* b, float* pdf, float* cos_in, void* stream)
+{
+  (void)unit;
+  return eval_pdf_table_world_common(t, call_flags, material, nx, ny, nz, nullptr, nullptr, nullptr, in_x, in_y, in_z,
+                                     out_x, out_y, out_z, mask, n, component, r, g, b, pdf, cos_in, stream);
+}
+
+int bbm_hip_eval_pdf_table_world_tangent(const bbm_hip_table* t, int call_flags, const uint32_t* material,
+                                         const float* nx, const float* ny, const float* nz,
+                                         const float* tx, const float* ty, const float* tz,
+                                         const float* in_x, const float* in_y, const float* in_z,
+                                         const float* out_x, const float* out_y, const float* out_z,
+                                         const uint8_t* mask, size_t n, uint32_t component, uint32_t unit,
+                                         float* r, float* g, float* b, float* pdf, float* cos_in, void* stream)
+{
+  (void)unit;
+  bool tangent;
+  if (const int rc = tangent_arg(tx, ty, tz, tangent)) return rc;
+  return eval_pdf_table_world_common(t, call_flags, material, nx, ny, nz, tx, ty, tz, in_x, in_y, in_z,
+                                     out_x, out_y, out_z, mask, n, component, r, g, b, pdf, cos_in, stream);
 }
 
 int bbm_hip_sample_table(const bbm_hip_table* t, int call_flags, const uint32_t* material,
@@ -760,6 +889,7 @@ int bbm_hip_sample_table(const bbm_hip_table* t, int call_flags, const uint32_t*
 
 static int sample_eval_table_common(bool world, const bbm_hip_table* t, int call_flags, const uint32_t* material,
                                     const float* nx, const float* ny, const float* nz,
+                                    const float* tx, const float* ty, const float* tz,
                                     const float* out_x, const float* out_y, const float* out_z,
                                     const float* xi0, const float* xi1,
                                     const uint8_t* mask, size_t n, uint32_t component,
@@ -782,6 +912,14 @@ static int sample_eval_table_common(bool world, const bbm_hip_table* t, int call
   a.src = {t->prepared, material, t->count};
   if (!world) return t->e->run.sample_eval_tab(a, static_cast<hipStream_t>(stream));
   a.e.nx = nx; a.e.ny = ny; a.e.nz = nz;
+  if (tx && t->e->tangent.sample_eval_tab)
+  {
+    SampleEvalTabTangentArgs ta;
+    static_cast<SampleEvalArgs&>(ta.e) = a.e;
+    ta.e.tx = tx; ta.e.ty = ty; ta.e.tz = tz;
+    ta.src = a.src;
+    return t->e->tangent.sample_eval_tab(ta, static_cast<hipStream_t>(stream));
+  }
   return t->e->run.sample_eval_tab_world(a, static_cast<hipStream_t>(stream));
 }
 
@@ -793,8 +931,9 @@ int bbm_hip_sample_eval_table(const bbm_hip_table* t, int call_flags, const uint
                               float* r, float* g, float* b, float* wr, float* wg, float* wb, void* stream)
 {
   (void)unit;
-  return sample_eval_table_common(false, t, call_flags, material, nullptr, nullptr, nullptr, out_x, out_y, out_z, xi0,
-                                  xi1, mask, n, component, dir_x, dir_y, dir_z, pdf, flag, r, g, b, wr, wg, wb, stream);
+  return sample_eval_table_common(false, t, call_flags, material, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+                                  out_x, out_y, out_z, xi0, xi1, mask, n, component, dir_x, dir_y, dir_z, pdf, flag,
+                                  r, g, b, wr, wg, wb, stream);
 }
 
 int bbm_hip_sample_eval_table_world(const bbm_hip_table* t, int call_flags, const uint32_t* material,
@@ -806,8 +945,25 @@ int bbm_hip_sample_eval_table_world(const bbm_hip_table* t, int call_flags, cons
                                     float* r, float* g, float* b, float* wr, float* wg, float* wb, void* stream)
 {
   (void)unit;
-  return sample_eval_table_common(true, t, call_flags, material, nx, ny, nz, out_x, out_y, out_z, xi0, xi1, mask, n,
-                                  component, dir_x, dir_y, dir_z, pdf, flag, r, g, b, wr, wg, wb, stream);
+  return sample_eval_table_common(true, t, call_flags, material, nx, ny, nz, nullptr, nullptr, nullptr, out_x, out_y,
+                                  out_z, xi0, xi1, mask, n, component, dir_x, dir_y, dir_z, pdf, flag, r, g, b, wr, wg,
+                                  wb, stream);
+}
+
+int bbm_hip_sample_eval_table_world_tangent(const bbm_hip_table* t, int call_flags, const uint32_t* material,
+                                            const float* nx, const float* ny, const float* nz,
+                                            const float* tx, const float* ty, const float* tz,
+                                            const float* out_x, const float* out_y, const float* out_z,
+                                            const float* xi0, const float* xi1,
+                                            const uint8_t* mask, size_t n, uint32_t component, uint32_t unit,
+                                            float* dir_x, float* dir_y, float* dir_z, float* pdf, uint32_t* flag,
+                                            float* r, float* g, float* b, float* wr, float* wg, float* wb, void* stream)
+{
+  (void)unit;
+  bool tangent;
+  if (const int rc = tangent_arg(tx, ty, tz, tangent)) return rc;
+  return sample_eval_table_common(true, t, call_flags, material, nx, ny, nz, tx, ty, tz, out_x, out_y, out_z, xi0, xi1,
+                                  mask, n, component, dir_x, dir_y, dir_z, pdf, flag, r, g, b, wr, wg, wb, stream);
 }
 
 int bbm_hip_reflectance_table(const bbm_hip_table* t, int call_flags, const uint32_t* material,
@@ -899,6 +1055,25 @@ void move_out(SetMoveArgs& m, void* sorted, void* lanes)
 {
   m.from[m.count] = static_cast<const uint32_t*>(sorted);
   m.to[m.count++] = static_cast<uint32_t*>(lanes);
+}
+
+// whether a row of the set reads a tangent (bbm_hip_model_anisotropic); without one the tangent is not gathered
+bool set_any_anisotropic(const bbm_hip_set& set)
+{
+  for (const bbm_hip_table* t : set.tables)
+    if (t->e->tangent.eval_pdf_tab) return true;
+  return false;
+}
+
+// The tangent's gather, a launch of its own beside `in`'s (k_set_gather carries kSetMaxIn streams, which the normal,
+// `in` and `out` fill): the same order and slots, no mask.
+void set_tangent_streams(SetMoveArgs& tan_in, const SetMoveArgs& in, const float* tx, const float* ty, const float* tz,
+                         float** sorted, SetScratch& scratch)
+{
+  std::memset(&tan_in, 0, sizeof(tan_in));
+  tan_in.src = in.src; tan_in.n = in.n; tan_in.capacity = in.capacity;
+  const float* lanes[3] = {tx, ty, tz};
+  for (int c = 0; c < 3; ++c) move_in(tan_in, lanes[c], sorted[c] = scratch.stream4());
 }
 
 }  // namespace
@@ -1051,17 +1226,20 @@ int bbm_hip_set_plan_segments(const bbm_hip_set_plan* plan, uint64_t* out, uint3
 
 const uint32_t* bbm_hip_set_plan_order(const bbm_hip_set_plan* plan) { return plan ? plan->src : nullptr; }
 
-int bbm_hip_set_eval_pdf(const bbm_hip_set_plan* plan, int call_flags,
-                         const float* nx, const float* ny, const float* nz,
-                         const float* in_x, const float* in_y, const float* in_z,
-                         const float* out_x, const float* out_y, const float* out_z,
-                         const uint8_t* mask, size_t n, uint32_t component, uint32_t unit,
-                         float* r, float* g, float* b, float* pdf, float* cos_in, void* stream)
+// tx, ty, tz: all set (bbm_hip_set_eval_pdf_tangent) or all NULL
+static int set_eval_pdf_common(const bbm_hip_set_plan* plan, int call_flags,
+                               const float* nx, const float* ny, const float* nz,
+                               const float* tx, const float* ty, const float* tz,
+                               const float* in_x, const float* in_y, const float* in_z,
+                               const float* out_x, const float* out_y, const float* out_z,
+                               const uint8_t* mask, size_t n, uint32_t component, uint32_t unit,
+                               float* r, float* g, float* b, float* pdf, float* cos_in, void* stream)
 {
   bool done, world;
   int rc = set_call(plan, call_flags, n, done);
   if (rc || done) return rc;
   if ((rc = set_normal(nx, ny, nz, world))) return rc;
+  if (tx && !world) return fail(BBM_HIP_ERR_INVALID_ARG, "tangent needs a normal: it fills the frame of the world-space call");
   if (cos_in && !world) return fail(BBM_HIP_ERR_INVALID_ARG, "cos_in needs a normal: it is the cosine of `in` against it");
   EvalArgs checked;
   int mode = 0;
@@ -1074,10 +1252,11 @@ int bbm_hip_set_eval_pdf(const bbm_hip_set_plan* plan, int call_flags,
   const hipStream_t s = static_cast<hipStream_t>(stream);
   const bool eval = mode & kModeEval, want_pdf = mode & kModePdf;
   SetScratch scratch;
-  if ((rc = scratch.acquire(capacity, (world ? 9 : 6) + (eval ? 3 : 0) + (want_pdf ? 1 : 0) + (cos_in ? 1 : 0),
-                            mask != nullptr, s)))
+  const bool tangent = tx && set_any_anisotropic(set);
+  if ((rc = scratch.acquire(capacity, (world ? 9 : 6) + (tangent ? 3 : 0) + (eval ? 3 : 0) + (want_pdf ? 1 : 0) +
+                                          (cos_in ? 1 : 0), mask != nullptr, s)))
     return rc;
-  SetMoveArgs in, out;
+  SetMoveArgs in, out, tan_in;
   std::memset(&in, 0, sizeof(in));
   in.src = plan->src; in.n = plan->n; in.capacity = capacity;
   out = in;
@@ -1088,9 +1267,12 @@ int bbm_hip_set_eval_pdf(const bbm_hip_set_plan* plan, int call_flags,
   float* sres[5] = {};
   for (int c = 0; c < 5; ++c)
     if (res[c]) move_out(out, sres[c] = scratch.stream4(), res[c]);
+  float* stan[3] = {};
+  if (tangent) set_tangent_streams(tan_in, in, tx, ty, tz, stan, scratch);
   uint8_t* smask = mask ? scratch.take<uint8_t>(capacity) : nullptr;
   in.mask_from = mask; in.mask_to = smask;
   if ((rc = set_gather_launch(in, s))) return rc;
+  if (tangent && (rc = set_gather_launch(tan_in, s))) return rc;
   for (uint32_t k = 0; k < rows; ++k)
   {
     const size_t o = plan->seg[k], nk = plan->seg[k + 1] - o;
@@ -1098,14 +1280,109 @@ int bbm_hip_set_eval_pdf(const bbm_hip_set_plan* plan, int call_flags,
     const auto at = [o](float* p) { return p ? p + o : nullptr; };
     const uint8_t* mk = smask ? smask + o : nullptr;
     if (world)
-      rc = bbm_hip_eval_pdf_table_world(set.tables[k], call_flags, plan->local + o, sorted[0] + o, sorted[1] + o,
-                                        sorted[2] + o, sorted[3] + o, sorted[4] + o, sorted[5] + o, sorted[6] + o,
-                                        sorted[7] + o, sorted[8] + o, mk, nk, component, unit, at(sres[0]), at(sres[1]),
-                                        at(sres[2]), at(sres[3]), at(sres[4]), stream);
+      rc = eval_pdf_table_world_common(set.tables[k], call_flags, plan->local + o, sorted[0] + o, sorted[1] + o,
+                                       sorted[2] + o, at(stan[0]), at(stan[1]), at(stan[2]), sorted[3] + o,
+                                       sorted[4] + o, sorted[5] + o, sorted[6] + o, sorted[7] + o, sorted[8] + o, mk,
+                                       nk, component, at(sres[0]), at(sres[1]), at(sres[2]), at(sres[3]), at(sres[4]),
+                                       stream);
     else
       rc = bbm_hip_eval_pdf_table(set.tables[k], call_flags, plan->local + o, sorted[3] + o, sorted[4] + o,
                                   sorted[5] + o, sorted[6] + o, sorted[7] + o, sorted[8] + o, mk, nk, component, unit,
                                   at(sres[0]), at(sres[1]), at(sres[2]), at(sres[3]), stream);
+    if (rc) return rc;
+  }
+  return set_scatter_launch(out, s);
+}
+
+int bbm_hip_set_eval_pdf(const bbm_hip_set_plan* plan, int call_flags,
+                         const float* nx, const float* ny, const float* nz,
+                         const float* in_x, const float* in_y, const float* in_z,
+                         const float* out_x, const float* out_y, const float* out_z,
+                         const uint8_t* mask, size_t n, uint32_t component, uint32_t unit,
+                         float* r, float* g, float* b, float* pdf, float* cos_in, void* stream)
+{
+  return set_eval_pdf_common(plan, call_flags, nx, ny, nz, nullptr, nullptr, nullptr, in_x, in_y, in_z, out_x, out_y,
+                             out_z, mask, n, component, unit, r, g, b, pdf, cos_in, stream);
+}
+
+int bbm_hip_set_eval_pdf_tangent(const bbm_hip_set_plan* plan, int call_flags,
+                                 const float* nx, const float* ny, const float* nz,
+                                 const float* tx, const float* ty, const float* tz,
+                                 const float* in_x, const float* in_y, const float* in_z,
+                                 const float* out_x, const float* out_y, const float* out_z,
+                                 const uint8_t* mask, size_t n, uint32_t component, uint32_t unit,
+                                 float* r, float* g, float* b, float* pdf, float* cos_in, void* stream)
+{
+  bool tangent;
+  if (const int rc = tangent_arg(tx, ty, tz, tangent)) return rc;
+  return set_eval_pdf_common(plan, call_flags, nx, ny, nz, tx, ty, tz, in_x, in_y, in_z, out_x, out_y, out_z, mask, n,
+                             component, unit, r, g, b, pdf, cos_in, stream);
+}
+
+static int set_sample_eval_common(const bbm_hip_set_plan* plan, int call_flags,
+                                  const float* nx, const float* ny, const float* nz,
+                                  const float* tx, const float* ty, const float* tz,
+                                  const float* out_x, const float* out_y, const float* out_z,
+                                  const float* xi0, const float* xi1,
+                                  const uint8_t* mask, size_t n, uint32_t component,
+                                  float* dir_x, float* dir_y, float* dir_z, float* pdf, uint32_t* flag,
+                                  float* r, float* g, float* b, float* wr, float* wg, float* wb, void* stream)
+{
+  bool done, world;
+  int rc = set_call(plan, call_flags, n, done);
+  if (rc || done) return rc;
+  if ((rc = set_normal(nx, ny, nz, world))) return rc;
+  if (tx && !world) return fail(BBM_HIP_ERR_INVALID_ARG, "tangent needs a normal: it fills the frame of the world-space call");
+  SampleEvalArgs checked;
+  if ((rc = sample_eval_args(out_x, out_y, out_z, xi0, xi1, mask, n, component, dir_x, dir_y, dir_z, pdf, flag,
+                             r, g, b, wr, wg, wb, checked)))
+    return rc;
+  const bbm_hip_set& set = *plan->set;
+  const uint32_t rows = set.rows.rows, capacity = plan->seg[rows];
+  for (uint32_t k = 0; k < rows; ++k)
+    if (!set.tables[k]->e->run.sample_eval_tab || (world && !set.tables[k]->e->run.sample_eval_tab_world))
+      return fail(BBM_HIP_ERR_UNSUPPORTED, std::string(set.tables[k]->e->name) + ": no material-table kernels");
+  const hipStream_t s = static_cast<hipStream_t>(stream);
+  SetScratch scratch;
+  const bool tangent = tx && set_any_anisotropic(set);
+  if ((rc = scratch.acquire(capacity, (world ? 8 : 5) + (tangent ? 3 : 0) + 5 + (r ? 3 : 0) + (wr ? 3 : 0),
+                            mask != nullptr, s)))
+    return rc;
+  SetMoveArgs in, out, tan_in;
+  std::memset(&in, 0, sizeof(in));
+  in.src = plan->src; in.n = plan->n; in.capacity = capacity;
+  out = in;
+  const float* lanes[8] = {nx, ny, nz, out_x, out_y, out_z, xi0, xi1};
+  float* sorted[8] = {};
+  for (int c = world ? 0 : 3; c < 8; ++c) move_in(in, lanes[c], sorted[c] = scratch.stream4());
+  void* res[11] = {dir_x, dir_y, dir_z, pdf, flag, r, g, b, wr, wg, wb};
+  float* sres[11] = {};
+  for (int c = 0; c < 11; ++c)
+    if (res[c]) move_out(out, sres[c] = scratch.stream4(), res[c]);
+  float* stan[3] = {};
+  if (tangent) set_tangent_streams(tan_in, in, tx, ty, tz, stan, scratch);
+  uint8_t* smask = mask ? scratch.take<uint8_t>(capacity) : nullptr;
+  in.mask_from = mask; in.mask_to = smask;
+  if ((rc = set_gather_launch(in, s))) return rc;
+  if (tangent && (rc = set_gather_launch(tan_in, s))) return rc;
+  for (uint32_t k = 0; k < rows; ++k)
+  {
+    const size_t o = plan->seg[k], nk = plan->seg[k + 1] - o;
+    if (nk == 0) continue;
+    const auto at = [o](float* p) { return p ? p + o : nullptr; };
+    const uint8_t* mk = smask ? smask + o : nullptr;
+    uint32_t* fl = reinterpret_cast<uint32_t*>(sres[4]) + o;
+    if (world)
+      rc = sample_eval_table_common(true, set.tables[k], call_flags, plan->local + o, sorted[0] + o, sorted[1] + o,
+                                    sorted[2] + o, at(stan[0]), at(stan[1]), at(stan[2]), sorted[3] + o, sorted[4] + o,
+                                    sorted[5] + o, sorted[6] + o, sorted[7] + o, mk, nk, component, at(sres[0]),
+                                    at(sres[1]), at(sres[2]), at(sres[3]), fl, at(sres[5]), at(sres[6]), at(sres[7]),
+                                    at(sres[8]), at(sres[9]), at(sres[10]), stream);
+    else
+      rc = bbm_hip_sample_eval_table(set.tables[k], call_flags, plan->local + o, sorted[3] + o, sorted[4] + o,
+                                     sorted[5] + o, sorted[6] + o, sorted[7] + o, mk, nk, component, 0u, at(sres[0]),
+                                     at(sres[1]), at(sres[2]), at(sres[3]), fl, at(sres[5]), at(sres[6]), at(sres[7]),
+                                     at(sres[8]), at(sres[9]), at(sres[10]), stream);
     if (rc) return rc;
   }
   return set_scatter_launch(out, s);
@@ -1119,57 +1396,25 @@ int bbm_hip_set_sample_eval(const bbm_hip_set_plan* plan, int call_flags,
                             float* dir_x, float* dir_y, float* dir_z, float* pdf, uint32_t* flag,
                             float* r, float* g, float* b, float* wr, float* wg, float* wb, void* stream)
 {
-  bool done, world;
-  int rc = set_call(plan, call_flags, n, done);
-  if (rc || done) return rc;
-  if ((rc = set_normal(nx, ny, nz, world))) return rc;
-  SampleEvalArgs checked;
-  if ((rc = sample_eval_args(out_x, out_y, out_z, xi0, xi1, mask, n, component, dir_x, dir_y, dir_z, pdf, flag,
-                             r, g, b, wr, wg, wb, checked)))
-    return rc;
-  const bbm_hip_set& set = *plan->set;
-  const uint32_t rows = set.rows.rows, capacity = plan->seg[rows];
-  for (uint32_t k = 0; k < rows; ++k)
-    if (!set.tables[k]->e->run.sample_eval_tab || (world && !set.tables[k]->e->run.sample_eval_tab_world))
-      return fail(BBM_HIP_ERR_UNSUPPORTED, std::string(set.tables[k]->e->name) + ": no material-table kernels");
-  const hipStream_t s = static_cast<hipStream_t>(stream);
-  SetScratch scratch;
-  if ((rc = scratch.acquire(capacity, (world ? 8 : 5) + 5 + (r ? 3 : 0) + (wr ? 3 : 0), mask != nullptr, s))) return rc;
-  SetMoveArgs in, out;
-  std::memset(&in, 0, sizeof(in));
-  in.src = plan->src; in.n = plan->n; in.capacity = capacity;
-  out = in;
-  const float* lanes[8] = {nx, ny, nz, out_x, out_y, out_z, xi0, xi1};
-  float* sorted[8] = {};
-  for (int c = world ? 0 : 3; c < 8; ++c) move_in(in, lanes[c], sorted[c] = scratch.stream4());
-  void* res[11] = {dir_x, dir_y, dir_z, pdf, flag, r, g, b, wr, wg, wb};
-  float* sres[11] = {};
-  for (int c = 0; c < 11; ++c)
-    if (res[c]) move_out(out, sres[c] = scratch.stream4(), res[c]);
-  uint8_t* smask = mask ? scratch.take<uint8_t>(capacity) : nullptr;
-  in.mask_from = mask; in.mask_to = smask;
-  if ((rc = set_gather_launch(in, s))) return rc;
-  for (uint32_t k = 0; k < rows; ++k)
-  {
-    const size_t o = plan->seg[k], nk = plan->seg[k + 1] - o;
-    if (nk == 0) continue;
-    const auto at = [o](float* p) { return p ? p + o : nullptr; };
-    const uint8_t* mk = smask ? smask + o : nullptr;
-    uint32_t* fl = reinterpret_cast<uint32_t*>(sres[4]) + o;
-    if (world)
-      rc = bbm_hip_sample_eval_table_world(set.tables[k], call_flags, plan->local + o, sorted[0] + o, sorted[1] + o,
-                                           sorted[2] + o, sorted[3] + o, sorted[4] + o, sorted[5] + o, sorted[6] + o,
-                                           sorted[7] + o, mk, nk, component, unit, at(sres[0]), at(sres[1]), at(sres[2]),
-                                           at(sres[3]), fl, at(sres[5]), at(sres[6]), at(sres[7]), at(sres[8]),
-                                           at(sres[9]), at(sres[10]), stream);
-    else
-      rc = bbm_hip_sample_eval_table(set.tables[k], call_flags, plan->local + o, sorted[3] + o, sorted[4] + o,
-                                     sorted[5] + o, sorted[6] + o, sorted[7] + o, mk, nk, component, unit, at(sres[0]),
-                                     at(sres[1]), at(sres[2]), at(sres[3]), fl, at(sres[5]), at(sres[6]), at(sres[7]),
-                                     at(sres[8]), at(sres[9]), at(sres[10]), stream);
-    if (rc) return rc;
-  }
-  return set_scatter_launch(out, s);
+  (void)unit;
+  return set_sample_eval_common(plan, call_flags, nx, ny, nz, nullptr, nullptr, nullptr, out_x, out_y, out_z, xi0, xi1,
+                                mask, n, component, dir_x, dir_y, dir_z, pdf, flag, r, g, b, wr, wg, wb, stream);
+}
+
+int bbm_hip_set_sample_eval_tangent(const bbm_hip_set_plan* plan, int call_flags,
+                                    const float* nx, const float* ny, const float* nz,
+                                    const float* tx, const float* ty, const float* tz,
+                                    const float* out_x, const float* out_y, const float* out_z,
+                                    const float* xi0, const float* xi1,
+                                    const uint8_t* mask, size_t n, uint32_t component, uint32_t unit,
+                                    float* dir_x, float* dir_y, float* dir_z, float* pdf, uint32_t* flag,
+                                    float* r, float* g, float* b, float* wr, float* wg, float* wb, void* stream)
+{
+  (void)unit;
+  bool tangent;
+  if (const int rc = tangent_arg(tx, ty, tz, tangent)) return rc;
+  return set_sample_eval_common(plan, call_flags, nx, ny, nz, tx, ty, tz, out_x, out_y, out_z, xi0, xi1, mask, n,
+                                component, dir_x, dir_y, dir_z, pdf, flag, r, g, b, wr, wg, wb, stream);
 }
 
 // ------------------------------------------------------------------------------- doubleRGB (f64.hip)

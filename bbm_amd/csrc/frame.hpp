@@ -3,8 +3,14 @@
 // kernels (frame.hip, and the world-space sample_eval kernels of sample_eval.hpp) share.
 //
 // toGlobalShadingFrame(n) is the matrix with columns X, Y, Z, Z = normalize(n); to_global is M v and to_local is
-// transpose(M) v (toLocalShadingFrame).  The tangent follows from the normal; a caller-supplied tangent would be
-// another way to fill X and Y.
+// transpose(M) v (toLocalShadingFrame).  X and Y are filled in one of two ways:
+//   shading_frame(n)      from the normal alone (Duff et al.), the reference's frame;
+//   tangent_frame(n, t)   from the normal and a world-space tangent t of any length, for the models
+//                         whose parameters run along X and Y.  Z, rn and live are shading_frame(n)'s.  With
+//                         d = dot3(Z, t), p = t - Z * d and pp = dot3(p, p): where pp > epsilon (tangent_live; a NaN
+//                         is not), X = p * (1 / sqrt(pp)) and Y = cross(Z, X), right-handed (X x Y = Z) as the Duff
+//                         frame is; elsewhere -- a zero tangent, one parallel to the normal, one shorter than about
+//                         3.5e-4, a NaN -- the frame is shading_frame(n)'s, bit for bit.
 #pragma once
 #include "math.hpp"
 
@@ -57,11 +63,35 @@ __device__ __forceinline__ Frame shading_frame(v3 n)
   return frame_scaled(n, div_nr(1.0f, sqrt_nr(nn)), nn > kEpsF);
 }
 
-// One lane of the frame calls: the vector in the other frame, 0 where the lane is masked or its frame is not live.
-template<bool TO_LOCAL>
-__device__ __forceinline__ v3 frame_apply(v3 n, v3 v, bool active)
+// The frame of a shading normal and a tangent, both of any length (the rule is at the head of this file): t's part
+// perpendicular to the normal, normalized, is X; where it has none to speak of the frame is shading_frame(n)'s.
+__device__ __forceinline__ Frame tangent_frame(v3 n, v3 t)
 {
   const Frame f = shading_frame(n);
+  const v3 Z = f.Z;
+  const float d = dot3(Z, t);
+  const v3 p = mk3(t.x - Z.x * d, t.y - Z.y * d, t.z - Z.z * d);
+  const float pp = dot3(p, p);
+  const bool tangent_live = pp > kEpsF;
+  const float rp = div_nr(1.0f, sqrt_nr(pp));
+  const v3 X = mk3(p.x * rp, p.y * rp, p.z * rp);
+  const v3 Y = cross3(Z, X);
+  return Frame{tangent_live ? X : f.X, tangent_live ? Y : f.Y, Z, f.live};
+}
+
+// the frame of a lane: the tangent is looked at only where the kernel was built with one
+template<bool TANGENT>
+__device__ __forceinline__ Frame lane_shading_frame(v3 n, v3 t)
+{
+  if constexpr (TANGENT) return tangent_frame(n, t);
+  else return shading_frame(n);
+}
+
+// One lane of the frame calls: the vector in the other frame, 0 where the lane is masked or its frame is not live.
+template<bool TO_LOCAL, bool TANGENT = false>
+__device__ __forceinline__ v3 frame_apply(v3 n, v3 v, bool active, v3 t = mk3(0.0f, 0.0f, 0.0f))
+{
+  const Frame f = lane_shading_frame<TANGENT>(n, t);
   const v3 r = TO_LOCAL ? f.to_local(v) : f.to_global(v);
   return (active && f.live) ? r : mk3(0.0f, 0.0f, 0.0f);
 }
@@ -74,7 +104,13 @@ struct FrameArgs
   uint64_t n;
   float* rx; float* ry; float* rz;
 };
+// the tangent frame calls (bbm_hip_frame_to_local_tangent / _to_global_tangent)
+struct FrameTangentArgs : FrameArgs
+{
+  const float* tx; const float* ty; const float* tz;   // the tangent per lane, any length
+};
 
 int frame_launch(const FrameArgs& a, bool to_local, hipStream_t s);     // frame.hip
+int frame_launch(const FrameTangentArgs& a, bool to_local, hipStream_t s);
 
 }  // namespace bbmhip

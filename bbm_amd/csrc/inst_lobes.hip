@@ -5,4 +5,5 @@
 
 namespace bbmhip {
 BBM_HIP_LOBE_MODELS(BBM_HIP_INSTANTIATE)
+BBM_HIP_LOBE_TANGENT_MODELS(BBM_HIP_INSTANTIATE_TANGENT)
 }  // namespace bbmhip

@@ -5,4 +5,5 @@
 
 namespace bbmhip {
 BBM_HIP_MICROFACET_MODELS(BBM_HIP_INSTANTIATE)
+BBM_HIP_MICROFACET_TANGENT_MODELS(BBM_HIP_INSTANTIATE_TANGENT)
 }  // namespace bbmhip

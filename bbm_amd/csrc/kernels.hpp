@@ -145,6 +145,26 @@ __device__ __forceinline__ bool frame_pair(v3 normal, bool on, v3& in, v3& out)
   out = in_frame ? lo : mk3(0.0f, 0.0f, 0.0f);
   return in_frame;
 }
+// The same in the frame of a normal and a tangent (tangent_frame), as two bbm_hip_frame_to_local_tangent calls
+// return it.  A function of its own, not a shared body: the normal-only kernels' code is then the text above alone.
+__device__ __forceinline__ bool frame_pair(v3 normal, v3 tangent, bool on, v3& in, v3& out)
+{
+  const Frame f = tangent_frame(normal, tangent);
+  const bool in_frame = on && f.live;
+  const v3 li = f.to_local(in), lo = f.to_local(out);
+  in = in_frame ? li : mk3(0.0f, 0.0f, 0.0f);
+  out = in_frame ? lo : mk3(0.0f, 0.0f, 0.0f);
+  return in_frame;
+}
+
+// The tangent form of the world-space eval calls (bbm_hip_eval_pdf_world_tangent and its table twin; DESIGN.md
+// §4.20), for the rows whose parameters run along the frame's X and Y (anisotropic, models.hpp).  A type of its own:
+// EvalWorldArgs is what the normal-only kernels take and stays as it is.
+struct EvalTangentArgs : EvalWorldArgs
+{
+  const float* tx; const float* ty; const float* tz;   // the tangent per lane, any length
+};
+template<class W> constexpr bool tangent_args = std::is_same_v<W, EvalTangentArgs>;
 
 // `on`: the lane's mask; `src_live`: a table lane's material index in range (it switches the component alone, as in
 // the local table call), true for the uniform call
@@ -155,6 +175,19 @@ __device__ __forceinline__ void one_pair_world(const Model& m, const EvalWorldAr
   float rgb[3], pdf;
   v3 in = mk3(a.ix[i], a.iy[i], a.iz[i]), out = mk3(a.ox[i], a.oy[i], a.oz[i]);
   const bool in_frame = frame_pair(mk3(w.nx[i], w.ny[i], w.nz[i]), on, in, out);
+  model_eval_pdf<MODE, EXACT>(m, in, out, (in_frame && src_live) ? a.component : 0u, rgb, pdf);
+  if (MODE & kModeEval) { a.r[i] = rgb[0]; a.g[i] = rgb[1]; a.b[i] = rgb[2]; }
+  if (MODE & kModePdf) a.pdf[i] = pdf;
+  if (w.cos) w.cos[i] = in.z;
+}
+// the tangent form's lane
+template<class Model, int MODE, bool EXACT = false>
+__device__ __forceinline__ void one_pair_world(const Model& m, const EvalTangentArgs& w, uint64_t i, bool on, bool src_live)
+{
+  const EvalArgs& a = w.e;
+  float rgb[3], pdf;
+  v3 in = mk3(a.ix[i], a.iy[i], a.iz[i]), out = mk3(a.ox[i], a.oy[i], a.oz[i]);
+  const bool in_frame = frame_pair(mk3(w.nx[i], w.ny[i], w.nz[i]), mk3(w.tx[i], w.ty[i], w.tz[i]), on, in, out);
   model_eval_pdf<MODE, EXACT>(m, in, out, (in_frame && src_live) ? a.component : 0u, rgb, pdf);
   if (MODE & kModeEval) { a.r[i] = rgb[0]; a.g[i] = rgb[1]; a.b[i] = rgb[2]; }
   if (MODE & kModePdf) a.pdf[i] = pdf;
@@ -1247,6 +1280,10 @@ using SampleEvalLauncher = int (*)(const SampleEvalArgs&, hipStream_t);
 using SampleEvalTabLauncher = int (*)(const SampleEvalTabArgs&, hipStream_t);
 using EvalWorldLauncher = int (*)(const EvalWorldArgs&, int, hipStream_t);
 using EvalTabWorldLauncher = int (*)(const EvalTabWorldArgs&, int, hipStream_t);
+using SampleEvalTangentLauncher = int (*)(const SampleEvalTangentArgs&, hipStream_t);
+using SampleEvalTabTangentLauncher = int (*)(const SampleEvalTabTangentArgs&, hipStream_t);
+using EvalTangentLauncher = int (*)(const EvalTangentArgs&, int, hipStream_t);
+using EvalTabTangentLauncher = int (*)(const EvalTabTangentArgs&, int, hipStream_t);
 
 // A composition's launchers: what a registry row (registry.hip) holds of its kernels.
 struct Launchers
@@ -1276,6 +1313,26 @@ struct Launchers
   EvalWorldLauncher eval_pdf_world;
   EvalTabWorldLauncher eval_pdf_tab_world;
 };
+// The tangent forms of the world-space calls: all null but for the anisotropic rows (models.hpp);
+// on every other row a tangent call is the normal-only call.
+struct TangentLaunchers
+{
+  SampleEvalTangentLauncher sample_eval;
+  SampleEvalTabTangentLauncher sample_eval_tab;
+  EvalTangentLauncher eval_pdf;
+  EvalTabTangentLauncher eval_pdf_tab;
+};
+template<class M> struct anisotropic;     // models.hpp
+template<class M> constexpr TangentLaunchers tangent_launchers()
+{
+  if constexpr (anisotropic<M>::value)
+  {
+    static_assert(supports_varying<M>::value, "every anisotropic row has table kernels");
+    return {&launch_sample_eval_tangent<M>, &launch_sample_eval_tab_tangent<M>, &launch_eval_pdf_tangent<M>,
+            &launch_eval_pdf_tab_tangent<M>};
+  }
+  else return {};
+}
 template<class M> constexpr Launchers launchers()
 {
   if constexpr (supports_varying<M>::value)

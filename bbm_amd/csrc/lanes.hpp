@@ -44,7 +44,11 @@ struct ReflTabArgs : LaneArgs<ReflArgs, TabRef> {};
 // EvalWorldArgs.  The frame is a property of the argument type (lane_frame), so the local instantiations keep their
 // names and hold nothing of it.  Instantiated for TabRef only: there is no world-space call over rows.
 struct EvalTabWorldArgs : LaneArgs<EvalWorldArgs, TabRef> {};
-template<class A> constexpr bool lane_frame = std::is_same_v<typename A::Call, EvalWorldArgs>;
+// Its tangent form (bbm_hip_eval_pdf_table_world_tangent): the frame of a normal and a tangent per
+// lane (lane_tangent), for the anisotropic rows only.
+struct EvalTabTangentArgs : LaneArgs<EvalTangentArgs, TabRef> {};
+template<class A> constexpr bool lane_tangent = std::is_same_v<typename A::Call, EvalTangentArgs>;
+template<class A> constexpr bool lane_frame = std::is_same_v<typename A::Call, EvalWorldArgs> || lane_tangent<A>;
 
 template<class Model, int MODE, bool EXACT, class A>
 __device__ __forceinline__ void lane_one_pair(const A& a, uint64_t i)
@@ -86,6 +90,8 @@ void k_eval_lane4(A a)
     const float4 ox = ld4<true>(e.ox, t), oy = ld4<true>(e.oy, t), oz = ld4<true>(e.oz, t);
     float4 wx = {}, wy = {}, wz = {};
     if constexpr (lane_frame<A>) { wx = ld4<true>(a.e.nx, t); wy = ld4<true>(a.e.ny, t); wz = ld4<true>(a.e.nz, t); }
+    float4 tx = {}, ty = {}, tz = {};
+    if constexpr (lane_tangent<A>) { tx = ld4<true>(a.e.tx, t); ty = ld4<true>(a.e.ty, t); tz = ld4<true>(a.e.tz, t); }
     const auto c = a.src.template load_quad<S>(t);
     const uint32_t mk = e.mask ? reinterpret_cast<const uint32_t*>(e.mask)[t] : 0x01010101u;
     float inx[4] = {ix.x, ix.y, ix.z, ix.w}, iny[4] = {iy.x, iy.y, iy.z, iy.w}, inz[4] = {iz.x, iz.y, iz.z, iz.w};
@@ -99,7 +105,12 @@ void k_eval_lane4(A a)
       for (int j = 0; j < 4; ++j)
       {
         v3 in = mk3(inx[j], iny[j], inz[j]), out = mk3(onx[j], ony[j], onz[j]);
-        in_frame[j] = frame_pair(mk3(nnx[j], nny[j], nnz[j]), ((mk >> (8 * j)) & 0xffu) != 0, in, out);
+        if constexpr (lane_tangent<A>)
+        {
+          const float ttx[4] = {tx.x, tx.y, tx.z, tx.w}, tty[4] = {ty.x, ty.y, ty.z, ty.w}, ttz[4] = {tz.x, tz.y, tz.z, tz.w};
+          in_frame[j] = frame_pair(mk3(nnx[j], nny[j], nnz[j]), mk3(ttx[j], tty[j], ttz[j]), ((mk >> (8 * j)) & 0xffu) != 0, in, out);
+        }
+        else in_frame[j] = frame_pair(mk3(nnx[j], nny[j], nnz[j]), ((mk >> (8 * j)) & 0xffu) != 0, in, out);
         inx[j] = in.x; iny[j] = in.y; inz[j] = in.z;
         onx[j] = out.x; ony[j] = out.y; onz[j] = out.z;
       }
@@ -264,9 +275,12 @@ struct LaneHost
 // Whether the quad form is used for aligned arrays: the source's choice, and for the world-space table call its own
 // on top of that (eval_tab_world_quad, judged per mode from the resource report; models.hpp).
 template<class Model, int MODE, bool EXACT> struct eval_tab_world_quad { static constexpr bool value = true; };
+// the tangent form's, judged on top of it
+template<class Model, int MODE, bool EXACT> struct eval_tab_tangent_quad : eval_tab_world_quad<Model, MODE, EXACT> {};
 template<class Model, int MODE, bool EXACT, class A> constexpr bool lane_quad()
 {
-  if constexpr (lane_frame<A>) return A::Src::template quad<Model> && eval_tab_world_quad<Model, MODE, EXACT>::value;
+  if constexpr (lane_tangent<A>) return A::Src::template quad<Model> && eval_tab_tangent_quad<Model, MODE, EXACT>::value;
+  else if constexpr (lane_frame<A>) return A::Src::template quad<Model> && eval_tab_world_quad<Model, MODE, EXACT>::value;
   else return A::Src::template quad<Model>;
 }
 
@@ -283,6 +297,7 @@ int launch_lane_kernel(const A& a, hipStream_t s)
   if (MODE & kModeEval) vec = vec && aligned16(e.r) && aligned16(e.g) && aligned16(e.b);
   if (MODE & kModePdf) vec = vec && aligned16(e.pdf);
   if constexpr (lane_frame<A>) vec = vec && aligned16(a.e.nx) && aligned16(a.e.ny) && aligned16(a.e.nz) && aligned16(a.e.cos);
+  if constexpr (lane_tangent<A>) vec = vec && aligned16(a.e.tx) && aligned16(a.e.ty) && aligned16(a.e.tz);
   const unsigned blocks = var_blocks(vec ? (e.n >> 2) : e.n);
   if (blocks == 0) return var_launched(blocks);
   if constexpr (quad)

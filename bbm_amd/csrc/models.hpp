@@ -254,6 +254,30 @@ BBM_HIP_WORLD_ONE_LANE_T(AggNganLafortuneM)
 template<class M, int MODE, bool EXACT> requires compact_eval<M>::value
 struct eval_world_quad<M, MODE, EXACT> { static constexpr bool value = false; };
 
+// The rows whose x and y roughness, sharpness or lobe coefficients run along the shading frame's X and Y: the
+// tangent forms of the world-space calls exist for these alone.  For every other row -- the fused
+// Aggregate<Lambertian, X> rows included, none of which has an anisotropic child -- value and pdf do not depend on
+// the rotation about the normal, and a tangent call is the normal-only call.
+template<class M> struct anisotropic { static constexpr bool value = false; };
+#define BBM_HIP_ANISOTROPIC(M) template<> struct anisotropic<M> { static constexpr bool value = true; };
+BBM_HIP_ANISOTROPIC(WardM)
+BBM_HIP_ANISOTROPIC(WardDuerM)
+BBM_HIP_ANISOTROPIC(WardDGMM)
+BBM_HIP_ANISOTROPIC(CookTorranceHeitzM)
+BBM_HIP_ANISOTROPIC(GGXHeitzM)
+BBM_HIP_ANISOTROPIC(RibardiereAnisoM)
+BBM_HIP_ANISOTROPIC(LafortuneM)
+BBM_HIP_ANISOTROPIC(ASM)
+BBM_HIP_ANISOTROPIC(ASFullM)
+
+// The tangent kernels, judged on top of the world kernels' choice from the compiler's resource report (the table in
+// DESIGN.md §4.20): a quad that spills with the tangent's twelve floats on top where its one-lane form does not runs
+// one lane per thread.
+// Two do (profiles/tangent_resources.txt): WardDuerGeislerMoroder's uniform quad (12 B) and RibardiereAnisotropic's
+// exact-mode table quad (20 B); no eval_pdf quad gains scratch or AGPRs, the frame being dead before the model runs.
+template<> struct sample_eval_tangent_quad<WardDGMM, false> { static constexpr bool value = false; };
+template<> struct sample_eval_tab_tangent_quad<RibardiereAnisoM, true> { static constexpr bool value = false; };
+
 }  // namespace bbmhip
 
 // X(composition) per instantiation unit
@@ -271,6 +295,10 @@ struct eval_world_quad<M, MODE, EXACT> { static constexpr bool value = false; };
 #define BBM_HIP_AGGREGATE_MODELS(X) \
   X(AggBagherM) X(AggCookTorranceM) X(AggGGXM) X(AggLowASM) X(AggLowMicrofacetM) X(AggLowSmoothM) X(AggNganASM) \
   X(AggPhongM) X(AggNganCookTorranceM) X(AggNganLafortuneM) X(AggNganWardM) X(AggNganWardDuerM) X(AggNganHeM)
+
+// the anisotropic rows (anisotropic<M>), per unit: the tangent forms of the world-space calls
+#define BBM_HIP_MICROFACET_TANGENT_MODELS(X) X(CookTorranceHeitzM) X(GGXHeitzM) X(RibardiereAnisoM)
+#define BBM_HIP_LOBE_TANGENT_MODELS(X) X(WardM) X(WardDuerM) X(WardDGMM) X(LafortuneM) X(ASM) X(ASFullM)
 
 #define BBM_HIP_INSTANTIATE(M)                                                   \
   template int launch_eval_pdf<M>(const EvalArgs&, int, hipStream_t);           \
@@ -312,3 +340,14 @@ struct eval_world_quad<M, MODE, EXACT> { static constexpr bool value = false; };
   extern template int launch_sample_eval_tab_world<M>(const SampleEvalTabArgs&, hipStream_t); \
   extern template int launch_eval_pdf_world<M>(const EvalWorldArgs&, int, hipStream_t); \
   extern template int launch_eval_pdf_tab_world<M>(const EvalTabWorldArgs&, int, hipStream_t);
+#define BBM_HIP_INSTANTIATE_TANGENT(M)                                         \
+  static_assert(anisotropic<M>::value, "tangent kernels are for the anisotropic rows"); \
+  template int launch_sample_eval_tangent<M>(const SampleEvalTangentArgs&, hipStream_t); \
+  template int launch_sample_eval_tab_tangent<M>(const SampleEvalTabTangentArgs&, hipStream_t); \
+  template int launch_eval_pdf_tangent<M>(const EvalTangentArgs&, int, hipStream_t); \
+  template int launch_eval_pdf_tab_tangent<M>(const EvalTabTangentArgs&, int, hipStream_t);
+#define BBM_HIP_EXTERN_TANGENT(M)                                              \
+  extern template int launch_sample_eval_tangent<M>(const SampleEvalTangentArgs&, hipStream_t); \
+  extern template int launch_sample_eval_tab_tangent<M>(const SampleEvalTabTangentArgs&, hipStream_t); \
+  extern template int launch_eval_pdf_tangent<M>(const EvalTangentArgs&, int, hipStream_t); \
+  extern template int launch_eval_pdf_tab_tangent<M>(const EvalTabTangentArgs&, int, hipStream_t);

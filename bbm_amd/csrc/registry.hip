@@ -21,6 +21,8 @@ BBM_HIP_AGGREGATE_MODELS(BBM_HIP_EXTERN)
 BBM_HIP_EPD_MODELS(BBM_HIP_EXTERN)
 BBM_HIP_HE_MODELS(BBM_HIP_EXTERN)
 BBM_HIP_MERL_MODELS(BBM_HIP_EXTERN)
+BBM_HIP_MICROFACET_TANGENT_MODELS(BBM_HIP_EXTERN_TANGENT)
+BBM_HIP_LOBE_TANGENT_MODELS(BBM_HIP_EXTERN_TANGENT)
 
 // Merl is measured data in float: no doubleRGB kernel
 template<> struct f64::has_f64<Merl> { static constexpr bool value = false; };
@@ -43,7 +45,7 @@ ModelEntry row(const char* name, uint32_t components, const char* layout, const 
                const float (&lower)[N], const float (&upper)[N], const char (&attrs)[N + 1])
 {
   static_assert(M::kParams == N, "registry nparams must match the composition");
-  ModelEntry e{name, N, components, launchers<M>(), f64_launchers<M>(), layout, {}, {}, {}, attrs};
+  ModelEntry e{name, N, components, launchers<M>(), f64_launchers<M>(), layout, {}, {}, {}, attrs, tangent_launchers<M>()};
   for (int i = 0; i < N; ++i)
   {
     e.defaults[i] = defaults[i]; e.lower[i] = lower[i]; e.upper[i] = upper[i];
@@ -340,6 +342,13 @@ int bbm_hip_model_has_table(int model_id)
   const ModelEntry* e = entry(model_id);
   if (!e) return unknown_id(model_id);
   return e->run.eval_pdf_tab ? 1 : 0;
+}
+
+int bbm_hip_model_anisotropic(int model_id)
+{
+  const ModelEntry* e = entry(model_id);
+  if (!e) return unknown_id(model_id);
+  return e->tangent.eval_pdf ? 1 : 0;
 }
 
 const char* bbm_hip_model_layout(int model_id)

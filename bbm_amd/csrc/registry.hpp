@@ -22,6 +22,7 @@ struct ModelEntry
   // per-parameter bsdf_attr flags (include/bbm/bsdf_attr_flag.h:16-29), one letter per parameter:
   // d DiffuseScale, D DiffuseParameter, s SpecularScale, p SpecularParameter, x Dependent
   const char* attrs;
+  TangentLaunchers tangent;      // all null but for the anisotropic rows (bbm_hip_model_anisotropic)
 };
 
 // a registry id, or a fused aggregate's id with BBM_HIP_RUNTIME_AGGREGATE (its aggregatebsdf semantics)

@@ -30,6 +30,15 @@ struct SampleEvalArgs
   const float* nx; const float* ny; const float* nz;   // the world-space calls' shading normal per lane, else null
 };
 struct SampleEvalTabArgs : LaneArgs<SampleEvalArgs, TabRef> {};     // e.s.p: the fallback block (table.hpp)
+// The tangent form of the world-space calls (bbm_hip_sample_eval_world_tangent and its table twin),
+// for the rows whose parameters run along the frame's X and Y (anisotropic, models.hpp).  Types of their own: the
+// local and normal-only kernels take SampleEvalArgs, which stays as it is.
+struct SampleEvalTangentArgs : SampleEvalArgs
+{
+  const float* tx; const float* ty; const float* tz;   // the tangent per lane, any length
+};
+struct SampleEvalTabTangentArgs : LaneArgs<SampleEvalTangentArgs, TabRef> {};
+template<class E> constexpr bool sample_eval_tangent = std::is_same_v<E, SampleEvalTangentArgs>;
 
 template<class Model> constexpr bool fused_sample_eval()
 {
@@ -73,14 +82,16 @@ __device__ __forceinline__ void sample_weight(const float* rgb, float dz, float 
 // masked lane of the local call after frame_to_local's 0, and its direction is frame_to_global's 0; `src_live`
 // (a table lane's material index in range) switches the component alone, as in the local table call.  cosz is the
 // local dir.z, the weight's cosine.  Without FRAME this is model_sample_eval and nothing else.
-template<bool FRAME, bool EXACT, class Model>
+// TANGENT (with FRAME): the frame is tangent_frame(normal, tangent), the staged calls the tangent frame calls.
+template<bool FRAME, bool EXACT, bool TANGENT = false, class Model>
 __device__ __forceinline__ void frame_sample_eval(const Model& m, v3 normal, v3 out, float xi0, float xi1, bool on,
                                                   bool src_live, uint32_t component, v3& dir, float& cosz, float* rgb,
-                                                  float& pdf, uint32_t& flag)
+                                                  float& pdf, uint32_t& flag, v3 tangent = mk3(0.0f, 0.0f, 0.0f))
 {
+  static_assert(FRAME || !TANGENT, "a tangent belongs to a world-space call");
   if constexpr (FRAME)
   {
-    const Frame f = shading_frame(normal);
+    const Frame f = lane_shading_frame<TANGENT>(normal, tangent);
     const bool in_frame = on && f.live;
     const v3 lo = f.to_local(out);
     v3 d;
@@ -98,15 +109,17 @@ __device__ __forceinline__ void frame_sample_eval(const Model& m, v3 normal, v3 
 }
 
 // `on`: the lane's mask; `src_live`: see frame_sample_eval (true for the uniform call)
-template<bool FRAME, bool EXACT, class Model>
-__device__ __forceinline__ void one_sample_eval(const Model& m, const SampleEvalArgs& a, uint64_t i, bool on,
-                                                bool src_live)
+template<bool FRAME, bool EXACT, class Model, class E>
+__device__ __forceinline__ void one_sample_eval(const Model& m, const E& a, uint64_t i, bool on, bool src_live)
 {
+  constexpr bool TAN = sample_eval_tangent<E>;
   const SampleArgs& s = a.s;
   v3 d; float rgb[3], pdf, cz; uint32_t f;
   const v3 nrm = FRAME ? mk3(a.nx[i], a.ny[i], a.nz[i]) : mk3(0.0f, 0.0f, 0.0f);
-  frame_sample_eval<FRAME, EXACT>(m, nrm, mk3(s.ox[i], s.oy[i], s.oz[i]), s.xi0[i], s.xi1[i], on, src_live,
-                                  s.component, d, cz, rgb, pdf, f);
+  v3 tan = mk3(0.0f, 0.0f, 0.0f);
+  if constexpr (TAN) tan = mk3(a.tx[i], a.ty[i], a.tz[i]);
+  frame_sample_eval<FRAME, EXACT, TAN>(m, nrm, mk3(s.ox[i], s.oy[i], s.oz[i]), s.xi0[i], s.xi1[i], on, src_live,
+                                       s.component, d, cz, rgb, pdf, f, tan);
   s.dx[i] = d.x; s.dy[i] = d.y; s.dz[i] = d.z; s.pdf[i] = pdf; s.flag[i] = f;
   if (a.r) { a.r[i] = rgb[0]; a.g[i] = rgb[1]; a.b[i] = rgb[2]; }
   if (a.wr)
@@ -128,14 +141,19 @@ template<class Model, bool EXACT> struct sample_eval_tab_quad { static constexpr
 // the local kernels' choice.  Specialised in models.hpp.
 template<class Model, bool EXACT> struct sample_eval_world_quad : sample_eval_quad<Model, EXACT> {};
 template<class Model, bool EXACT> struct sample_eval_tab_world_quad : sample_eval_tab_quad<Model, EXACT> {};
-template<bool FRAME, class Model, bool EXACT> constexpr bool sample_eval_use_quad()
+// The tangent form, judged again on top of the world kernels' choice.  Specialised in models.hpp.
+template<class Model, bool EXACT> struct sample_eval_tangent_quad : sample_eval_world_quad<Model, EXACT> {};
+template<class Model, bool EXACT> struct sample_eval_tab_tangent_quad : sample_eval_tab_world_quad<Model, EXACT> {};
+template<bool FRAME, class Model, bool EXACT, bool TANGENT = false> constexpr bool sample_eval_use_quad()
 {
-  if constexpr (FRAME) return sample_eval_world_quad<Model, EXACT>::value;
+  if constexpr (TANGENT) return sample_eval_tangent_quad<Model, EXACT>::value;
+  else if constexpr (FRAME) return sample_eval_world_quad<Model, EXACT>::value;
   else return sample_eval_quad<Model, EXACT>::value;
 }
-template<bool FRAME, class Model, bool EXACT> constexpr bool sample_eval_tab_use_quad()
+template<bool FRAME, class Model, bool EXACT, bool TANGENT = false> constexpr bool sample_eval_tab_use_quad()
 {
-  if constexpr (FRAME) return sample_eval_tab_world_quad<Model, EXACT>::value;
+  if constexpr (TANGENT) return sample_eval_tab_tangent_quad<Model, EXACT>::value;
+  else if constexpr (FRAME) return sample_eval_tab_world_quad<Model, EXACT>::value;
   else return sample_eval_tab_quad<Model, EXACT>::value;
 }
 
@@ -182,10 +200,12 @@ __device__ __forceinline__ void store_sample_eval(const SampleEvalArgs& a, uint6
 // 4 lanes per thread-iteration: 5 x 16-byte loads (out xyz, xi0, xi1), 5 + 3 + 3 x 16-byte stores.  Requires every
 // array 16-byte aligned and the mask 4-byte aligned (checked on the host); the n % 4 tail runs scalar.
 // FRAME: three more loads (the normal).
-template<class Model, bool EXACT, bool FRAME>
-__global__ __launch_bounds__(kBlock) BBM_HIP_SAMPLE_EVAL_ATTR(Model) void k_sample_eval_v4(SampleEvalArgs a)
+// E = SampleEvalTangentArgs: three more again (the tangent).
+template<class Model, bool EXACT, bool FRAME, class E>
+__global__ __launch_bounds__(kBlock) BBM_HIP_SAMPLE_EVAL_ATTR(Model) void k_sample_eval_v4(E a)
 {
   math_tables_init();
+  constexpr bool TAN = sample_eval_tangent<E>;
   const Model m(a.s.p.v);
   const SampleArgs& s = a.s;
   const uint64_t n4 = s.n >> 2;
@@ -196,6 +216,9 @@ __global__ __launch_bounds__(kBlock) BBM_HIP_SAMPLE_EVAL_ATTR(Model) void k_samp
     const float4 x0 = ld4<true>(s.xi0, t), x1 = ld4<true>(s.xi1, t);
     float4 wx = {}, wy = {}, wz = {};
     if constexpr (FRAME) { wx = ld4<true>(a.nx, t); wy = ld4<true>(a.ny, t); wz = ld4<true>(a.nz, t); }
+    float4 tx = {}, ty = {}, tz = {};
+    if constexpr (TAN) { tx = ld4<true>(a.tx, t); ty = ld4<true>(a.ty, t); tz = ld4<true>(a.tz, t); }
+    const float ttx[4] = {tx.x, tx.y, tx.z, tx.w}, tty[4] = {ty.x, ty.y, ty.z, ty.w}, ttz[4] = {tz.x, tz.y, tz.z, tz.w};
     const uint32_t mk = s.mask ? reinterpret_cast<const uint32_t*>(s.mask)[t] : 0x01010101u;
     const float onx[4] = {ox.x, ox.y, ox.z, ox.w}, ony[4] = {oy.x, oy.y, oy.z, oy.w}, onz[4] = {oz.x, oz.y, oz.z, oz.w};
     const float u0[4] = {x0.x, x0.y, x0.z, x0.w}, u1[4] = {x1.x, x1.y, x1.z, x1.w};
@@ -207,8 +230,9 @@ __global__ __launch_bounds__(kBlock) BBM_HIP_SAMPLE_EVAL_ATTR(Model) void k_samp
     {
       v3 d;
       float f[3];
-      frame_sample_eval<FRAME, EXACT>(m, mk3(nnx[j], nny[j], nnz[j]), mk3(onx[j], ony[j], onz[j]), u0[j], u1[j],
-                                      ((mk >> (8 * j)) & 0xffu) != 0, true, s.component, d, cz[j], f, pd[j], fl[j]);
+      frame_sample_eval<FRAME, EXACT, TAN>(m, mk3(nnx[j], nny[j], nnz[j]), mk3(onx[j], ony[j], onz[j]), u0[j], u1[j],
+                                           ((mk >> (8 * j)) & 0xffu) != 0, true, s.component, d, cz[j], f, pd[j], fl[j],
+                                           mk3(ttx[j], tty[j], ttz[j]));
       dx[j] = d.x; dy[j] = d.y; dz[j] = d.z;
 #pragma unroll
       for (int c = 0; c < 3; ++c) rgb[c][j] = f[c];
@@ -223,8 +247,8 @@ __global__ __launch_bounds__(kBlock) BBM_HIP_SAMPLE_EVAL_ATTR(Model) void k_samp
 }
 
 // Scalar path for unaligned arrays.
-template<class Model, bool EXACT, bool FRAME>
-__global__ __launch_bounds__(kBlock) BBM_HIP_SAMPLE_EVAL_ATTR(Model) void k_sample_eval_v1(SampleEvalArgs a)
+template<class Model, bool EXACT, bool FRAME, class E>
+__global__ __launch_bounds__(kBlock) BBM_HIP_SAMPLE_EVAL_ATTR(Model) void k_sample_eval_v1(E a)
 {
   math_tables_init();
   const Model m(a.s.p.v);
@@ -253,6 +277,7 @@ template<class Model, int S, bool EXACT, bool FRAME, class A>
 __global__ __launch_bounds__(kBlock) BBM_HIP_SAMPLE_EVAL_ATTR(Model) void k_seval_lane4(A a)
 {
   math_tables_init();
+  constexpr bool TAN = sample_eval_tangent<typename A::Call>;
   const SampleArgs& s = a.e.s;
   const uint64_t n4 = s.n >> 2;
   const uint64_t t = uint64_t(blockIdx.x) * kBlock + threadIdx.x;
@@ -262,6 +287,9 @@ __global__ __launch_bounds__(kBlock) BBM_HIP_SAMPLE_EVAL_ATTR(Model) void k_seva
     const float4 x0 = ld4<true>(s.xi0, t), x1 = ld4<true>(s.xi1, t);
     float4 wx = {}, wy = {}, wz = {};
     if constexpr (FRAME) { wx = ld4<true>(a.e.nx, t); wy = ld4<true>(a.e.ny, t); wz = ld4<true>(a.e.nz, t); }
+    float4 tx = {}, ty = {}, tz = {};
+    if constexpr (TAN) { tx = ld4<true>(a.e.tx, t); ty = ld4<true>(a.e.ty, t); tz = ld4<true>(a.e.tz, t); }
+    const float ttx[4] = {tx.x, tx.y, tx.z, tx.w}, tty[4] = {ty.x, ty.y, ty.z, ty.w}, ttz[4] = {tz.x, tz.y, tz.z, tz.w};
     const auto c = a.src.template load_quad<S>(t);
     const uint32_t mk = s.mask ? reinterpret_cast<const uint32_t*>(s.mask)[t] : 0x01010101u;
     const float onx[4] = {ox.x, ox.y, ox.z, ox.w}, ony[4] = {oy.x, oy.y, oy.z, oy.w}, onz[4] = {oz.x, oz.y, oz.z, oz.w};
@@ -277,9 +305,9 @@ __global__ __launch_bounds__(kBlock) BBM_HIP_SAMPLE_EVAL_ATTR(Model) void k_seva
       const Model m(q.v);
       v3 d;
       float f[3];
-      frame_sample_eval<FRAME, EXACT>(m, mk3(nnx[j], nny[j], nnz[j]), mk3(onx[j], ony[j], onz[j]), u0[j], u1[j],
-                                      ((mk >> (8 * j)) & 0xffu) != 0, a.src.quad_live(c, j), s.component, d, cz[j], f,
-                                      pd[j], fl[j]);
+      frame_sample_eval<FRAME, EXACT, TAN>(m, mk3(nnx[j], nny[j], nnz[j]), mk3(onx[j], ony[j], onz[j]), u0[j], u1[j],
+                                           ((mk >> (8 * j)) & 0xffu) != 0, a.src.quad_live(c, j), s.component, d, cz[j],
+                                           f, pd[j], fl[j], mk3(ttx[j], tty[j], ttz[j]));
       dx[j] = d.x; dy[j] = d.y; dz[j] = d.z;
 #pragma unroll
       for (int c3 = 0; c3 < 3; ++c3) rgb[c3][j] = f[c3];
@@ -307,14 +335,18 @@ inline bool sample_eval_aligned(const SampleEvalArgs& a)
          aligned16(a.r) && aligned16(a.g) && aligned16(a.b) && aligned16(a.wr) && aligned16(a.wg) &&
          aligned16(a.wb) && aligned16(a.nx) && aligned16(a.ny) && aligned16(a.nz) && (reinterpret_cast<uintptr_t>(s.mask) & 3u) == 0;
 }
+inline bool sample_eval_aligned(const SampleEvalTangentArgs& a)
+{
+  return sample_eval_aligned(static_cast<const SampleEvalArgs&>(a)) && aligned16(a.tx) && aligned16(a.ty) && aligned16(a.tz);
+}
 
 // What the exact mode launches for a row: the sampler's twin where it has one (launch_sample_mask), evaluated with
 // the exact eval_pdf where the model has one (launch_mode) -- the two staged calls' choices, each on its own.
 template<class Model> constexpr bool sample_eval_has_exact() { return has_exact_sample<Model>() || model_has_exact<Model>(); }
 
 // One mode's launch: K the kernels' model type (the row's, or its sampler's exact twin), QUAD the mode's trait.
-template<class K, bool E, bool QUAD, bool FRAME>
-void launch_sample_eval_kernel(const SampleEvalArgs& a, hipStream_t s)
+template<class K, bool E, bool QUAD, bool FRAME, class Args>
+void launch_sample_eval_kernel(const Args& a, hipStream_t s)
 {
   const bool vec = QUAD && sample_eval_aligned(a);
   const uint64_t units = vec ? (a.s.n >> 2) : a.s.n;
@@ -323,17 +355,18 @@ void launch_sample_eval_kernel(const SampleEvalArgs& a, hipStream_t s)
   if (blocks > max_blocks()) blocks = max_blocks();
   if constexpr (QUAD)
   {
-    if (vec) hipLaunchKernelGGL((k_sample_eval_v4<K, E, FRAME>), dim3(unsigned(blocks)), dim3(kBlock), 0, s, a);
+    if (vec) hipLaunchKernelGGL((k_sample_eval_v4<K, E, FRAME, Args>), dim3(unsigned(blocks)), dim3(kBlock), 0, s, a);
   }
-  if (!vec) hipLaunchKernelGGL((k_sample_eval_v1<K, E, FRAME>), dim3(unsigned(blocks)), dim3(kBlock), 0, s, a);
+  if (!vec) hipLaunchKernelGGL((k_sample_eval_v1<K, E, FRAME, Args>), dim3(unsigned(blocks)), dim3(kBlock), 0, s, a);
 }
 
-template<class Model, bool FRAME>
-int launch_sample_eval_frame(const SampleEvalArgs& a0, hipStream_t s)
+template<class Model, bool FRAME, class Args>
+int launch_sample_eval_frame(const Args& a0, hipStream_t s)
 {
+  constexpr bool TAN = sample_eval_tangent<Args>;
   if (const int rc = host_prepare<Model>::run(s)) return rc;
   if (const int rc = host_validate<Model>::run(a0.s.p)) return rc;
-  SampleEvalArgs a = a0;
+  Args a = a0;
   void* scratch = nullptr;
   if (const int rc = host_params<Model>::run(a.s.p, a.s.component, s, &scratch)) return rc;
   struct Release { void* p; hipStream_t s; ~Release() { host_params<Model>::done(p, s); } } release{scratch, s};
@@ -342,10 +375,10 @@ int launch_sample_eval_frame(const SampleEvalArgs& a0, hipStream_t s)
     if (exact_on())
     {
       launch_sample_eval_kernel<exact_sample_t<Model>, model_has_exact<Model>(),
-                                sample_eval_use_quad<FRAME, Model, true>(), FRAME>(a, s);
+                                sample_eval_use_quad<FRAME, Model, true, TAN>(), FRAME>(a, s);
       exact = true;
     }
-  if (!exact) launch_sample_eval_kernel<Model, false, sample_eval_use_quad<FRAME, Model, false>(), FRAME>(a, s);
+  if (!exact) launch_sample_eval_kernel<Model, false, sample_eval_use_quad<FRAME, Model, false, TAN>(), FRAME>(a, s);
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) return fail(BBM_HIP_ERR_HIP, std::string("kernel launch failed: ") + hipGetErrorString(e));
   return BBM_HIP_OK;
@@ -354,41 +387,45 @@ int launch_sample_eval_frame(const SampleEvalArgs& a0, hipStream_t s)
 // the local call, and the world-space one (a.nx / ny / nz set)
 template<class Model> int launch_sample_eval(const SampleEvalArgs& a, hipStream_t s) { return launch_sample_eval_frame<Model, false>(a, s); }
 template<class Model> int launch_sample_eval_world(const SampleEvalArgs& a, hipStream_t s) { return launch_sample_eval_frame<Model, true>(a, s); }
+// the tangent form (a.tx / ty / tz set as well); instantiated for the anisotropic rows only
+template<class Model> int launch_sample_eval_tangent(const SampleEvalTangentArgs& a, hipStream_t s) { return launch_sample_eval_frame<Model, true>(a, s); }
 
 // a full grid, as the other per-lane kernels; 0 where the batch is too large for one launch (var_blocks)
-template<class K, int S, bool E, bool QUAD, bool FRAME>
-unsigned launch_sample_eval_tab_kernel(const SampleEvalTabArgs& a, hipStream_t s)
+template<class K, int S, bool E, bool QUAD, bool FRAME, class A>
+unsigned launch_sample_eval_tab_kernel(const A& a, hipStream_t s)
 {
   const bool vec = QUAD && sample_eval_aligned(a.e) && a.src.aligned(S);
   const unsigned blocks = var_blocks(vec ? (a.e.s.n >> 2) : a.e.s.n);
   if (blocks == 0) return blocks;
   if constexpr (QUAD)
   {
-    if (vec) hipLaunchKernelGGL((k_seval_lane4<K, S, E, FRAME, SampleEvalTabArgs>), dim3(blocks), dim3(kBlock), 0, s, a);
+    if (vec) hipLaunchKernelGGL((k_seval_lane4<K, S, E, FRAME, A>), dim3(blocks), dim3(kBlock), 0, s, a);
   }
-  if (!vec) hipLaunchKernelGGL((k_seval_lane1<K, S, E, FRAME, SampleEvalTabArgs>), dim3(blocks), dim3(kBlock), 0, s, a);
+  if (!vec) hipLaunchKernelGGL((k_seval_lane1<K, S, E, FRAME, A>), dim3(blocks), dim3(kBlock), 0, s, a);
   return blocks;
 }
 
 // The table's blocks were prepared at create (table_prepare: host_prepare, host_validate, host_params per material),
 // so, as for launch_sample_lanes, nothing is left to do on the host but choose the kernel.
-template<class Model, bool FRAME>
-int launch_sample_eval_tab_frame(const SampleEvalTabArgs& a, hipStream_t s)
+template<class Model, bool FRAME, class A>
+int launch_sample_eval_tab_frame(const A& a, hipStream_t s)
 {
   if constexpr (!supports_varying<Model>::value) return var_unsupported();
   else
   {
+    constexpr bool TAN = sample_eval_tangent<typename A::Call>;
     constexpr int S = table_slots<Model>::value;
     if constexpr (sample_eval_has_exact<Model>())
       if (exact_on())
         return var_launched(launch_sample_eval_tab_kernel<exact_sample_t<Model>, S, model_has_exact<Model>(),
-                                                          sample_eval_tab_use_quad<FRAME, Model, true>(), FRAME>(a, s));
-    return var_launched(launch_sample_eval_tab_kernel<Model, S, false, sample_eval_tab_use_quad<FRAME, Model, false>(),
+                                                          sample_eval_tab_use_quad<FRAME, Model, true, TAN>(), FRAME>(a, s));
+    return var_launched(launch_sample_eval_tab_kernel<Model, S, false, sample_eval_tab_use_quad<FRAME, Model, false, TAN>(),
                                                       FRAME>(a, s));
   }
 }
 
 template<class Model> int launch_sample_eval_tab(const SampleEvalTabArgs& a, hipStream_t s) { return launch_sample_eval_tab_frame<Model, false>(a, s); }
 template<class Model> int launch_sample_eval_tab_world(const SampleEvalTabArgs& a, hipStream_t s) { return launch_sample_eval_tab_frame<Model, true>(a, s); }
+template<class Model> int launch_sample_eval_tab_tangent(const SampleEvalTabTangentArgs& a, hipStream_t s) { return launch_sample_eval_tab_frame<Model, true>(a, s); }
 
 }  // namespace bbmhip

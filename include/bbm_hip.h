@@ -395,6 +395,78 @@ int bbm_hip_set_sample_eval(const bbm_hip_set_plan* plan, int call_flags,
                             float* dir_x, float* dir_y, float* dir_z, float* pdf, uint32_t* flag,
                             float* r, float* g, float* b, float* wr, float* wg, float* wb, void* stream);
 
+/* ---------------------------------------------------------------- world-space calls with a tangent per lane */
+
+/* The world-space calls above build the frame from the normal alone; its X and Y then follow the normal's sign branch.
+ * Nine models take their x and y roughness, sharpness or lobe coefficients along X and Y (Ward, WardDuer,
+ * WardDuerGeislerMoroder, CookTorranceHeitz, GGXHeitz, RibardiereAnisotropic, Lafortune, AshikhminShirley,
+ * AshikhminShirleyFull: bbm_hip_model_anisotropic).  For them each call below is its counterpart without `_tangent`
+ * with a world-space tangent per lane, (tx, ty, tz), any length, directly after the normal: with Z the normalized
+ * normal, p = t - Z (Z . t); where |p|^2 > epsilon, X = normalize(p) and Y = Z x X (right-handed, as the normal-only
+ * frame); elsewhere (a zero or NaN tangent, one parallel to the normal, one shorter than about 3.5e-4) the frame is
+ * the normal-only one, bit for bit.  For lane i every output equals, bit for bit, what the counterpart's staged
+ * sequence returns with bbm_hip_frame_to_local_tangent / bbm_hip_frame_to_global_tangent as the frame calls.
+ * For every other model a tangent call IS the normal-only call: the same outputs bit for bit, the tangent arrays not
+ * read (value and pdf of an isotropic model do not depend on the rotation about the normal, and its sampled direction
+ * is an equally valid sample).  Tangent pointers: all three NULL -> the counterpart itself; one or two NULL ->
+ * BBM_HIP_ERR_INVALID_ARG before anything else is looked at; every other check is the counterpart's.  In a set each
+ * row runs the tangent call where its model is anisotropic and the normal-only one elsewhere; the tangent needs the
+ * normal. */
+int bbm_hip_model_anisotropic(int model_id);            /* 1 / 0, <0 for an unknown id */
+int bbm_hip_frame_to_local_tangent(const float* nx, const float* ny, const float* nz,
+                                   const float* tx, const float* ty, const float* tz,
+                                   const float* x, const float* y, const float* z, const uint8_t* mask, size_t n,
+                                   float* lx, float* ly, float* lz, void* stream);
+int bbm_hip_frame_to_global_tangent(const float* nx, const float* ny, const float* nz,
+                                    const float* tx, const float* ty, const float* tz,
+                                    const float* lx, const float* ly, const float* lz, const uint8_t* mask, size_t n,
+                                    float* x, float* y, float* z, void* stream);
+int bbm_hip_sample_eval_world_tangent(int model_id, const float* params, int nparams,
+                                      const float* nx, const float* ny, const float* nz,
+                                      const float* tx, const float* ty, const float* tz,
+                                      const float* out_x, const float* out_y, const float* out_z,
+                                      const float* xi0, const float* xi1,
+                                      const uint8_t* mask, size_t n, uint32_t component, uint32_t unit,
+                                      float* dir_x, float* dir_y, float* dir_z, float* pdf, uint32_t* flag,
+                                      float* r, float* g, float* b, float* wr, float* wg, float* wb, void* stream);
+int bbm_hip_sample_eval_table_world_tangent(const bbm_hip_table* table, int call_flags, const uint32_t* material,
+                                            const float* nx, const float* ny, const float* nz,
+                                            const float* tx, const float* ty, const float* tz,
+                                            const float* out_x, const float* out_y, const float* out_z,
+                                            const float* xi0, const float* xi1,
+                                            const uint8_t* mask, size_t n, uint32_t component, uint32_t unit,
+                                            float* dir_x, float* dir_y, float* dir_z, float* pdf, uint32_t* flag,
+                                            float* r, float* g, float* b, float* wr, float* wg, float* wb, void* stream);
+int bbm_hip_eval_pdf_world_tangent(int model_id, const float* params, int nparams,
+                                   const float* nx, const float* ny, const float* nz,
+                                   const float* tx, const float* ty, const float* tz,
+                                   const float* in_x, const float* in_y, const float* in_z,
+                                   const float* out_x, const float* out_y, const float* out_z,
+                                   const uint8_t* mask, size_t n, uint32_t component, uint32_t unit,
+                                   float* r, float* g, float* b, float* pdf, float* cos_in, void* stream);
+int bbm_hip_eval_pdf_table_world_tangent(const bbm_hip_table* table, int call_flags, const uint32_t* material,
+                                         const float* nx, const float* ny, const float* nz,
+                                         const float* tx, const float* ty, const float* tz,
+                                         const float* in_x, const float* in_y, const float* in_z,
+                                         const float* out_x, const float* out_y, const float* out_z,
+                                         const uint8_t* mask, size_t n, uint32_t component, uint32_t unit,
+                                         float* r, float* g, float* b, float* pdf, float* cos_in, void* stream);
+int bbm_hip_set_eval_pdf_tangent(const bbm_hip_set_plan* plan, int call_flags,
+                                 const float* nx, const float* ny, const float* nz,
+                                 const float* tx, const float* ty, const float* tz,
+                                 const float* in_x, const float* in_y, const float* in_z,
+                                 const float* out_x, const float* out_y, const float* out_z,
+                                 const uint8_t* mask, size_t n, uint32_t component, uint32_t unit,
+                                 float* r, float* g, float* b, float* pdf, float* cos_in, void* stream);
+int bbm_hip_set_sample_eval_tangent(const bbm_hip_set_plan* plan, int call_flags,
+                                    const float* nx, const float* ny, const float* nz,
+                                    const float* tx, const float* ty, const float* tz,
+                                    const float* out_x, const float* out_y, const float* out_z,
+                                    const float* xi0, const float* xi1,
+                                    const uint8_t* mask, size_t n, uint32_t component, uint32_t unit,
+                                    float* dir_x, float* dir_y, float* dir_z, float* pdf, uint32_t* flag,
+                                    float* r, float* g, float* b, float* wr, float* wg, float* wb, void* stream);
+
 /* ---------------------------------------------------------------- doubleRGB (Value = double) */
 
 /* The reference's doubleRGB configuration (backbone/native/include/backbone.h:41-42: Value = double, Spectrum =
