@@ -85,6 +85,13 @@ SIGNATURES = {
     "bbm_hip_eval_pdf_table_world_tangent": (_I, [_P, _I, _P] + [_P] * 13 + [_SZ, _U32, _U32] + [_P] * 6),
     "bbm_hip_set_eval_pdf_tangent": (_I, [_P, _I] + [_P] * 13 + [_SZ, _U32, _U32] + [_P] * 6),
     "bbm_hip_set_sample_eval_tangent": (_I, [_P, _I] + [_P] * 12 + [_SZ, _U32, _U32] + [_P] * 12),
+    "bbm_hip_set_plan_create_compact": (_I, [_P, _P, _SZ, _P, _P]),
+    "bbm_hip_set_plan_compact": (_I, [_P]),
+    "bbm_hip_set_plan_gather": (_I, [_P, _P, _P, _I, _P, _P, _SZ, _P]),
+    "bbm_hip_set_plan_scatter": (_I, [_P, _P, _P, _I, _SZ, _P]),
+    "bbm_hip_set_gather_shape": (_I, [_I]),
+    "bbm_hip_set_eval_pdf_sorted": (_I, [_P, _I] + [_P] * 13 + [_SZ, _U32, _U32] + [_P] * 6),
+    "bbm_hip_set_sample_eval_sorted": (_I, [_P, _I] + [_P] * 12 + [_SZ, _U32, _U32] + [_P] * 12),
     "bbm_hip_model_has_f64": (_I, [_I]),
     "bbm_hip_eval_pdf_f64": (_I, [_I, _P, _I, _P, _P, _P, _P, _P, _P, _P, _SZ, _U32, _U32, _P, _P, _P, _P, _P]),
     "bbm_hip_sample_f64": (_I, [_I, _P, _I, _P, _P, _P, _P, _P, _P, _SZ, _U32, _U32, _P, _P, _P, _P, _P, _P]),

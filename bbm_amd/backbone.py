@@ -198,6 +198,11 @@ def _frame_fn(name, fptr):
     return getattr(_lib.load(), name + "_tangent" if fptr is not None and len(fptr) == 6 else name)
 
 
+def _frame6(fptr):
+    """The frame pointers of _frame_rows as the six the *_sorted calls take: normal, then tangent, NULL where absent."""
+    return tuple(fptr or ()) + (None,) * (6 - len(fptr or ()))
+
+
 def _world_normal(normal, cosine, varying, in_, out, tangent=None):
     """The world-space keywords of eval_pdf, checked ahead of every other argument: the frame's row pointers
     (_frame_rows), or None for the local call.  cosine and tangent need a normal; normal= excludes varying= and float64
@@ -1313,11 +1318,35 @@ class _DevicePtr:
         self.__cuda_array_interface__ = {"shape": (count,), "typestr": "<i4", "data": (ptr, False), "version": 2}
 
 
+def _four_byte_rows(t, length, device, what):
+    """A stream argument of MaterialPlan.gather / scatter: a CUDA tensor of a four-byte dtype on the plan's device,
+    shaped (length,) or (k, length) with contiguous rows -> the device pointer of every row."""
+    torch = _torch()
+    if not isinstance(t, torch.Tensor) or not t.is_cuda or t.element_size() != 4 or t.is_complex():
+        raise TypeError(f"{what}: expected a CUDA tensor of a four-byte dtype (float32, int32, uint32)")
+    if t.device != device:
+        raise TypeError(f"{what}: must live on {device}, got {t.device}")
+    if t.dim() not in (1, 2) or t.shape[-1] != length:
+        raise ValueError(f"{what}: expected shape ({length},) or (k, {length}), got {tuple(t.shape)}")
+    if length > 1 and t.stride(-1) != 1:
+        raise ValueError(f"{what}: rows must be contiguous")
+    if t.dim() == 1:
+        return [t.data_ptr()]
+    return [t.data_ptr() + 4 * r * t.stride(0) for r in range(t.shape[0])]
+
+
+def _ptr_array(ptrs):
+    return (ctypes.c_void_p * max(len(ptrs), 1))(*ptrs)
+
+
 class MaterialPlan:
     """The stable partition of one batch's lanes by table (bbm_hip_set_plan_*), made by
-    MaterialSet.plan and passed as `plan=` to any number of calls over the same hits."""
+    MaterialSet.plan and passed as `plan=` to any number of calls over the same hits.  drop=True makes the compact plan
+    (bbm_hip_set_plan_create_compact): a lane whose id is out of range is in no slot, and only the
+    calls with order="plan" take it.  `capacity` is the number of sorted slots (segments[-1]), `compact` whether lanes
+    were dropped.  gather / scatter carry any four-byte streams between lane order and slot order."""
 
-    def __init__(self, mset, material, stream=None):
+    def __init__(self, mset, material, stream=None, *, drop=False):
         torch = _torch()
         self._handle = None
         if not isinstance(material, torch.Tensor) or material.dim() != 1:
@@ -1326,20 +1355,84 @@ class MaterialPlan:
         idx = MaterialTable._material(material, n, material.device)
         _on_stream(stream, material)
         handle = ctypes.c_void_p()
-        _lib.check(_lib.load().bbm_hip_set_plan_create(mset._live(), idx, n, _stream_ptr(stream), ctypes.byref(handle)))
+        lib = _lib.load()
+        create = lib.bbm_hip_set_plan_create_compact if drop else lib.bbm_hip_set_plan_create
+        _lib.check(create(mset._live(), idx, n, _stream_ptr(stream), ctypes.byref(handle)))
         self._handle = handle
+        self.compact = bool(drop)
         self.set = mset
         self.device = material.device
         self.lanes = n
         seg = (ctypes.c_uint64 * (mset.rows + 1))()
         _lib.check(_lib.load().bbm_hip_set_plan_segments(handle, seg, mset.rows + 1))
         self.segments = [int(v) for v in seg]
+        self.capacity = self.segments[-1]
 
     def _live(self):
         if self._handle is None:
             raise ValueError("MaterialPlan: the plan is closed")
         self.set._live()
         return self._handle
+
+    def gather(self, *tensors, mask=None, stream=None):
+        """Lane order -> slot order (bbm_hip_set_plan_gather).  Each tensor: a CUDA tensor of a four-byte dtype shaped
+        (lanes,) or (k, lanes) with contiguous rows; -> tensors of shape (capacity,) or (k, capacity) of the same
+        dtypes, in argument order: slot j holds lane order()[j]'s element, a padding slot 0.  mask: a uint8 / bool
+        (lanes,) tensor, or True for "every lane live": the (capacity,) uint8 mask in slot order comes last, 0 in
+        padding slots.  One tensor and no mask: that tensor alone, not a tuple."""
+        torch = _torch()
+        h = self._live()
+        n, cap, dev = self.lanes, self.capacity, self.device
+        src, outs = [], []
+        for k, t in enumerate(tensors):
+            src += _four_byte_rows(t, n, dev, f"gather: tensor {k}")
+            outs.append(torch.empty(t.shape[:-1] + (cap,), dtype=t.dtype, device=dev))
+        dst = [p for o in outs for p in _four_byte_rows(o, cap, dev, "gather: output")]
+        mfrom = mto = keep = None
+        if mask is not None and mask is not False:
+            if mask is not True:
+                mfrom, keep = _mask_ptr(mask, n)
+            mto = torch.empty((cap,), dtype=torch.uint8, device=dev)
+            outs.append(mto)
+        _on_stream(stream, keep, *tensors, *outs)
+        _lib.check(_lib.load().bbm_hip_set_plan_gather(
+            h, _ptr_array(src), _ptr_array(dst), len(src), mfrom, None if mto is None else mto.data_ptr(), n,
+            _stream_ptr(stream)))
+        return outs[0] if len(outs) == 1 else tuple(outs)
+
+    def scatter(self, *tensors, out=None, stream=None):
+        """Slot order -> lane order (bbm_hip_set_plan_scatter), the inverse of gather: tensors of shape (capacity,) or
+        (k, capacity) -> tensors of shape (lanes,) or (k, lanes).  Without out= the results start as zeros, so a lane
+        a compact plan dropped reads 0; with out= (a tuple of tensors of the results' shapes and dtypes) such lanes
+        keep what they held.  One tensor: that result alone, not a tuple."""
+        torch = _torch()
+        h = self._live()
+        n, cap, dev = self.lanes, self.capacity, self.device
+        if out is not None:
+            out = (out,) if isinstance(out, torch.Tensor) else tuple(out)
+            if len(out) != len(tensors):
+                raise ValueError(f"scatter: out= holds {len(out)} tensors for {len(tensors)} streams")
+        src, dst, outs, keep = [], [], [], []
+        for k, t in enumerate(tensors):
+            rows = _four_byte_rows(t, cap, dev, f"scatter: tensor {k}")
+            if any(p % 16 for p in rows):            # the slot-order side is read 16 bytes at a time
+                t = t.clone(memory_format=torch.contiguous_format)
+                rows = _four_byte_rows(t, cap, dev, f"scatter: tensor {k}")
+            keep.append(t)
+            src += rows
+            shape = t.shape[:-1] + (n,)
+            if out is None:
+                o = torch.zeros(shape, dtype=torch.int32, device=dev).view(t.dtype)
+            else:
+                o = out[k]
+                if not isinstance(o, torch.Tensor) or o.dtype != t.dtype or tuple(o.shape) != tuple(shape):
+                    raise ValueError(f"scatter: out[{k}]: expected a {t.dtype} tensor of shape {tuple(shape)}")
+            dst += _four_byte_rows(o, n, dev, f"scatter: out[{k}]")
+            outs.append(o)
+        _on_stream(stream, *keep, *outs)
+        _lib.check(_lib.load().bbm_hip_set_plan_scatter(h, _ptr_array(src), _ptr_array(dst), len(src), n,
+                                                        _stream_ptr(stream)))
+        return outs[0] if len(outs) == 1 else tuple(outs)
 
     def order(self):
         """The source lane of every sorted slot: an int32 CUDA tensor of the plan's capacity, -1 in padding slots."""
@@ -1416,9 +1509,24 @@ class MaterialSet:
             raise ValueError("MaterialSet: the set is closed")
         return self._handle
 
-    def plan(self, material, stream=None):
-        """Partition one batch's lanes by table: a MaterialPlan for `plan=`.  Waits for the stream once."""
-        return MaterialPlan(self, material, stream)
+    def plan(self, material, stream=None, *, drop=False):
+        """Partition one batch's lanes by table: a MaterialPlan for `plan=`.  Waits for the stream once.  drop=True:
+        the lanes whose id is out of range (terminated paths) are left out of the plan (MaterialPlan)."""
+        return MaterialPlan(self, material, stream, drop=drop)
+
+    @staticmethod
+    def _sorted(order, material, plan):
+        """order= of the calls: "lanes" (False) or "plan" (True), which needs plan= and excludes material=.  A compact
+        plan has no lane-order call: its dropped lanes would get no output."""
+        if order not in ("lanes", "plan"):
+            raise ValueError(f'order: expected "lanes" or "plan", got {order!r}')
+        if order == "plan":
+            if plan is None or material is not None:
+                raise ValueError('order="plan" needs plan= (and no material=): the streams are in that plan\'s slot order')
+            return True
+        if isinstance(plan, MaterialPlan) and plan.compact:
+            raise ValueError('a compact plan (drop=True) leaves lanes out: call it with order="plan"')
+        return False
 
     def _planned(self, material, plan, stream, n, device):
         """(the plan to use, whether it is this call's own)."""
@@ -1435,11 +1543,15 @@ class MaterialSet:
 
     def eval_pdf(self, in_, out, component=bsdf_flag.All, unit=unit_t.Radiance, mask=None, *, material=None,
                  plan=None, rgb=None, pdf=None, stream=None, mode=3, exact=None, normal=None, cosine=False,
-                 tangent=None):
-        """tangent (with normal=): read by the rows whose model is anisotropic (bbm_hip_set_eval_pdf_tangent)."""
+                 tangent=None, order="lanes"):
+        """tangent (with normal=): read by the rows whose model is anisotropic (bbm_hip_set_eval_pdf_tangent).
+        order="plan" (with plan=): every input, mask, normal, tangent, rgb= and pdf= is in the plan's slot order and of
+        length plan.capacity (MaterialPlan.gather), and so are the results: nothing is gathered or scattered
+        (bbm_hip_set_eval_pdf_sorted)."""
         nptr = _world_normal(normal, cosine, None, in_, out, tangent)
         if _is_f64(in_) or _is_f64(out):
             raise TypeError("MaterialSet: material sets are floatRGB only (float32 tensors)")
+        in_plan_order = self._sorted(order, material, plan)
         ix, iy, iz, n = _soa(in_, what="in")
         ox, oy, oz, _ = _soa(out, n, what="out")
         dev = _device(in_)
@@ -1449,8 +1561,10 @@ class MaterialSet:
         _on_stream(stream, _keep, rgb, pdf, cos)
         p, own = self._planned(material, plan, stream, n, dev)
         try:
-            _lib.check(_frame_fn("bbm_hip_set_eval_pdf", nptr)(
-                p._live(), MaterialTable._flags(exact), *(nptr or (None, None, None)), ix, iy, iz, ox, oy, oz, mptr, n,
+            fn, frame = ((_lib.load().bbm_hip_set_eval_pdf_sorted, _frame6(nptr)) if in_plan_order else
+                         (_frame_fn("bbm_hip_set_eval_pdf", nptr), nptr or (None, None, None)))
+            _lib.check(fn(
+                p._live(), MaterialTable._flags(exact), *frame, ix, iy, iz, ox, oy, oz, mptr, n,
                 int(component), int(unit), *_eval_pdf_ptrs(mode, rgb, pdf), None if cos is None else cos.data_ptr(),
                 _stream_ptr(stream)))
         finally:
@@ -1465,8 +1579,11 @@ class MaterialSet:
         return _with_cosine(self.eval_pdf(in_, out, component, unit, mask, mode=2, **kw), 1, kw.get("cosine", False))
 
     def sample_eval(self, out, xi, component=bsdf_flag.All, unit=unit_t.Radiance, mask=None, *, material=None,
-                    plan=None, value=True, weight=True, stream=None, exact=None, normal=None, tangent=None):
+                    plan=None, value=True, weight=True, stream=None, exact=None, normal=None, tangent=None,
+                    order="lanes"):
+        """order="plan": as eval_pdf's (bbm_hip_set_sample_eval_sorted)."""
         nptr = _frame_rows(normal, tangent, out)
+        in_plan_order = self._sorted(order, material, plan)
         ox, oy, oz, n, x0, x1 = _sample_eval_inputs(out, xi)
         dev = x0.device
         mptr, _keep = _mask_ptr(mask, n)
@@ -1475,8 +1592,10 @@ class MaterialSet:
         d, p_, f, v, w = outs
         p, own = self._planned(material, plan, stream, n, dev)
         try:
-            _lib.check(_frame_fn("bbm_hip_set_sample_eval", nptr)(
-                p._live(), MaterialTable._flags(exact), *(nptr or (None, None, None)), ox, oy, oz, x0.data_ptr(),
+            fn, frame = ((_lib.load().bbm_hip_set_sample_eval_sorted, _frame6(nptr)) if in_plan_order else
+                         (_frame_fn("bbm_hip_set_sample_eval", nptr), nptr or (None, None, None)))
+            _lib.check(fn(
+                p._live(), MaterialTable._flags(exact), *frame, ox, oy, oz, x0.data_ptr(),
                 x1.data_ptr(), mptr, n, int(component), int(unit), d[0].data_ptr(), d[1].data_ptr(), d[2].data_ptr(),
                 p_.data_ptr(), f.data_ptr(), *_row_ptrs(v), *_row_ptrs(w), _stream_ptr(stream)))
         finally:

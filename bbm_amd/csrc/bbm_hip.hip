@@ -995,11 +995,13 @@ struct bbm_hip_set
 };
 
 // The stable partition of n lanes by table.  src and local are one device allocation of 2 x slots uint32; seg is the
-// host copy of the segment starts (seg[rows] = capacity <= slots).
+// host copy of the segment starts (seg[rows] = capacity <= slots).  compact: the lanes whose id is out of range are in
+// no slot (bbm_hip_set_plan_create_compact).
 struct bbm_hip_set_plan
 {
   const bbm_hip_set* set;
   uint32_t n, slots;
+  bool compact;
   uint32_t* src;
   uint32_t* local;
   uint32_t seg[kSetMaxRows + 1];
@@ -1016,6 +1018,27 @@ int set_call(const bbm_hip_set_plan* p, int call_flags, size_t n, bool& done)
   if (n != p->n)
     return fail(BBM_HIP_ERR_INVALID_ARG, "n is " + std::to_string(n) + ", the plan was made for " + std::to_string(p->n) + " lanes");
   done = n == 0;
+  return BBM_HIP_OK;
+}
+
+// The lane-order calls scatter through src, which would leave a dropped lane's outputs unwritten.
+int set_lane_order(const bbm_hip_set_plan* p)
+{
+  if (p && p->compact)
+    return fail(BBM_HIP_ERR_INVALID_ARG, "a compact plan leaves lanes out: use the calls in plan order (the *_sorted calls)");
+  return BBM_HIP_OK;
+}
+
+// What the two calls in plan order check first: set_call's checks with the slots in place of the lanes.
+int set_sorted_call(const bbm_hip_set_plan* p, int call_flags, size_t slots, bool& done)
+{
+  done = false;
+  if (!p) return fail(BBM_HIP_ERR_INVALID_ARG, "plan is NULL");
+  if (const int rc = table_call(p->set->tables[0], call_flags, 0, nullptr)) return rc;
+  const size_t capacity = p->seg[p->set->rows.rows];
+  if (slots != capacity)
+    return fail(BBM_HIP_ERR_INVALID_ARG, "slots is " + std::to_string(slots) + ", the plan's capacity is " + std::to_string(capacity));
+  done = capacity == 0;
   return BBM_HIP_OK;
 }
 
@@ -1129,8 +1152,8 @@ int bbm_hip_set_plan_geometry(uint32_t* tile, uint32_t* scan_chunk)
   return BBM_HIP_OK;
 }
 
-int bbm_hip_set_plan_create(const bbm_hip_set* set, const uint32_t* material, size_t n, void* stream,
-                            bbm_hip_set_plan** out)
+static int set_plan_create_common(const bbm_hip_set* set, const uint32_t* material, size_t n, void* stream,
+                                  bbm_hip_set_plan** out, bool drop)
 {
   if (!set) return fail(BBM_HIP_ERR_INVALID_ARG, "set is NULL");
   if (!out) return fail(BBM_HIP_ERR_INVALID_ARG, "out is NULL");
@@ -1143,6 +1166,7 @@ int bbm_hip_set_plan_create(const bbm_hip_set* set, const uint32_t* material, si
   std::memset(p.get(), 0, sizeof(*p));
   p->set = set;
   p->n = uint32_t(n);
+  p->compact = drop;
   if (n == 0)
   {
     *out = p.release();
@@ -1157,6 +1181,7 @@ int bbm_hip_set_plan_create(const bbm_hip_set* set, const uint32_t* material, si
   a.n = p->n;
   a.groups = (p->n + kSetTile - 1) / kSetTile;
   a.slots = p->slots;
+  a.drop = drop ? 1u : 0u;
   hipError_t err = hipMalloc(reinterpret_cast<void**>(&p->src), size_t(p->slots) * 8u);
   if (err != hipSuccess)
   {
@@ -1200,6 +1225,23 @@ int bbm_hip_set_plan_create(const bbm_hip_set* set, const uint32_t* material, si
   return BBM_HIP_OK;
 }
 
+int bbm_hip_set_plan_create(const bbm_hip_set* set, const uint32_t* material, size_t n, void* stream,
+                            bbm_hip_set_plan** out)
+{
+  return set_plan_create_common(set, material, n, stream, out, false);
+}
+
+int bbm_hip_set_plan_create_compact(const bbm_hip_set* set, const uint32_t* material, size_t n, void* stream,
+                                    bbm_hip_set_plan** out)
+{
+  return set_plan_create_common(set, material, n, stream, out, true);
+}
+
+int bbm_hip_set_plan_compact(const bbm_hip_set_plan* plan)
+{
+  return plan ? int(plan->compact) : fail(BBM_HIP_ERR_INVALID_ARG, "plan is NULL");
+}
+
 int bbm_hip_set_plan_destroy(bbm_hip_set_plan* plan)
 {
   if (!plan) return BBM_HIP_OK;
@@ -1236,7 +1278,9 @@ static int set_eval_pdf_common(const bbm_hip_set_plan* plan, int call_flags,
                                float* r, float* g, float* b, float* pdf, float* cos_in, void* stream)
 {
   bool done, world;
-  int rc = set_call(plan, call_flags, n, done);
+  int rc = set_lane_order(plan);
+  if (rc) return rc;
+  rc = set_call(plan, call_flags, n, done);
   if (rc || done) return rc;
   if ((rc = set_normal(nx, ny, nz, world))) return rc;
   if (tx && !world) return fail(BBM_HIP_ERR_INVALID_ARG, "tangent needs a normal: it fills the frame of the world-space call");
@@ -1329,7 +1373,9 @@ static int set_sample_eval_common(const bbm_hip_set_plan* plan, int call_flags,
                                   float* r, float* g, float* b, float* wr, float* wg, float* wb, void* stream)
 {
   bool done, world;
-  int rc = set_call(plan, call_flags, n, done);
+  int rc = set_lane_order(plan);
+  if (rc) return rc;
+  rc = set_call(plan, call_flags, n, done);
   if (rc || done) return rc;
   if ((rc = set_normal(nx, ny, nz, world))) return rc;
   if (tx && !world) return fail(BBM_HIP_ERR_INVALID_ARG, "tangent needs a normal: it fills the frame of the world-space call");
@@ -1415,6 +1461,174 @@ int bbm_hip_set_sample_eval_tangent(const bbm_hip_set_plan* plan, int call_flags
   if (const int rc = tangent_arg(tx, ty, tz, tangent)) return rc;
   return set_sample_eval_common(plan, call_flags, nx, ny, nz, tx, ty, tz, out_x, out_y, out_z, xi0, xi1, mask, n,
                                 component, dir_x, dir_y, dir_z, pdf, flag, r, g, b, wr, wg, wb, stream);
+}
+
+// ---- material sets in plan order: the permute as a call of its own, and the two calls on streams
+// that are already in slot order
+
+// 0: k_set_gather (a stream at a time); 1: k_set_gather_batched.  Process-wide, for bbm_hip_set_plan_gather alone.
+static std::atomic<int>& set_gather_shape()
+{
+  static std::atomic<int> shape{0};
+  return shape;
+}
+
+int bbm_hip_set_gather_shape(int shape)
+{
+  if (shape != 0 && shape != 1) return fail(BBM_HIP_ERR_INVALID_ARG, "gather shape: 0 (a stream at a time) or 1 (batched)");
+  return set_gather_shape().exchange(shape);
+}
+
+// What gather and scatter check, in this order: count and the pointer arrays (which need no plan), the plan, n, and
+// for a plan that has slots every entry and the alignment of the slot-order side.  done: nothing to launch.
+static int set_move_check(const bbm_hip_set_plan* plan, const void* const* from, void* const* to, int count,
+                          const void* const* sorted, size_t n, bool& done)
+{
+  done = false;
+  if (count < 0) return fail(BBM_HIP_ERR_INVALID_ARG, "count is negative");
+  if (count > 0 && (!from || !to)) return fail(BBM_HIP_ERR_INVALID_ARG, "from or to is NULL");
+  if (!plan) return fail(BBM_HIP_ERR_INVALID_ARG, "plan is NULL");
+  if (n != plan->n)
+    return fail(BBM_HIP_ERR_INVALID_ARG, "n is " + std::to_string(n) + ", the plan was made for " + std::to_string(plan->n) + " lanes");
+  // an empty plan has no slot: its arrays hold nothing and may be NULL
+  if ((done = plan->seg[plan->set->rows.rows] == 0)) return BBM_HIP_OK;
+  for (int c = 0; c < count; ++c)
+    if (!from[c] || !to[c]) return fail(BBM_HIP_ERR_INVALID_ARG, "stream " + std::to_string(c) + ": a NULL pointer");
+  for (int c = 0; c < count; ++c)
+    if (reinterpret_cast<uintptr_t>(sorted[c]) & 15u)
+      return fail(BBM_HIP_ERR_INVALID_ARG, "stream " + std::to_string(c) + ": the array in slot order must be 16-byte aligned");
+  return BBM_HIP_OK;
+}
+
+int bbm_hip_set_plan_gather(const bbm_hip_set_plan* plan, const void* const* from, void* const* to, int count,
+                            const uint8_t* mask_from, uint8_t* mask_to, size_t n, void* stream)
+{
+  if (mask_from && !mask_to) return fail(BBM_HIP_ERR_INVALID_ARG, "mask_from without mask_to");
+  bool done;
+  if (const int rc = set_move_check(plan, from, to, count, const_cast<const void* const*>(to), n, done)) return rc;
+  if (done || (count == 0 && !mask_to)) return BBM_HIP_OK;
+  if (reinterpret_cast<uintptr_t>(mask_to) & 3u) return fail(BBM_HIP_ERR_INVALID_ARG, "mask_to must be 4-byte aligned");
+  const hipStream_t s = static_cast<hipStream_t>(stream);
+  const bool batched = set_gather_shape().load() == 1;
+  // kSetMaxIn streams a launch; the mask travels with the first
+  for (int first = 0; first == 0 || first < count; first += kSetMaxIn)
+  {
+    SetMoveArgs m;
+    std::memset(&m, 0, sizeof(m));
+    m.src = plan->src; m.n = plan->n; m.capacity = plan->seg[plan->set->rows.rows];
+    for (int c = first; c < count && c < first + kSetMaxIn; ++c) move_in(m, from[c], to[c]);
+    if (first == 0) { m.mask_from = mask_from; m.mask_to = mask_to; }
+    if (const int rc = batched ? set_gather_launch_batched(m, s) : set_gather_launch(m, s)) return rc;
+  }
+  return BBM_HIP_OK;
+}
+
+int bbm_hip_set_plan_scatter(const bbm_hip_set_plan* plan, const void* const* from, void* const* to, int count,
+                             size_t n, void* stream)
+{
+  bool done;
+  if (const int rc = set_move_check(plan, from, to, count, from, n, done)) return rc;
+  if (done) return BBM_HIP_OK;
+  const hipStream_t s = static_cast<hipStream_t>(stream);
+  for (int first = 0; first < count; first += kSetMaxOut)
+  {
+    SetMoveArgs m;
+    std::memset(&m, 0, sizeof(m));
+    m.src = plan->src; m.n = plan->n; m.capacity = plan->seg[plan->set->rows.rows];
+    for (int c = first; c < count && c < first + kSetMaxOut; ++c) move_out(m, const_cast<void*>(from[c]), to[c]);
+    if (const int rc = set_scatter_launch(m, s)) return rc;
+  }
+  return BBM_HIP_OK;
+}
+
+int bbm_hip_set_eval_pdf_sorted(const bbm_hip_set_plan* plan, int call_flags,
+                                const float* nx, const float* ny, const float* nz,
+                                const float* tx, const float* ty, const float* tz,
+                                const float* in_x, const float* in_y, const float* in_z,
+                                const float* out_x, const float* out_y, const float* out_z,
+                                const uint8_t* mask, size_t slots, uint32_t component, uint32_t unit,
+                                float* r, float* g, float* b, float* pdf, float* cos_in, void* stream)
+{
+  bool tangent, done, world;
+  int rc = tangent_arg(tx, ty, tz, tangent);
+  if (rc) return rc;
+  rc = set_sorted_call(plan, call_flags, slots, done);
+  if (rc || done) return rc;
+  if ((rc = set_normal(nx, ny, nz, world))) return rc;
+  if (tangent && !world) return fail(BBM_HIP_ERR_INVALID_ARG, "tangent needs a normal: it fills the frame of the world-space call");
+  if (cos_in && !world) return fail(BBM_HIP_ERR_INVALID_ARG, "cos_in needs a normal: it is the cosine of `in` against it");
+  EvalArgs checked;
+  int mode = 0;
+  if ((rc = eval_args(mode, in_x, in_y, in_z, out_x, out_y, out_z, mask, slots, component, r, g, b, pdf, checked))) return rc;
+  const bbm_hip_set& set = *plan->set;
+  const uint32_t rows = set.rows.rows;
+  for (uint32_t k = 0; world && k < rows; ++k)
+    if (!set.tables[k]->e->run.eval_pdf_tab_world)
+      return fail(BBM_HIP_ERR_UNSUPPORTED, std::string(set.tables[k]->e->name) + ": no material-table kernels");
+  for (uint32_t k = 0; k < rows; ++k)
+  {
+    const size_t o = plan->seg[k], nk = plan->seg[k + 1] - o;
+    if (nk == 0) continue;
+    const auto in = [o](const float* p) { return p ? p + o : nullptr; };
+    const auto at = [o](float* p) { return p ? p + o : nullptr; };
+    const uint8_t* mk = mask ? mask + o : nullptr;
+    if (world)
+      rc = eval_pdf_table_world_common(set.tables[k], call_flags, plan->local + o, nx + o, ny + o, nz + o, in(tx),
+                                       in(ty), in(tz), in_x + o, in_y + o, in_z + o, out_x + o, out_y + o, out_z + o,
+                                       mk, nk, component, at(r), at(g), at(b), at(pdf), at(cos_in), stream);
+    else
+      rc = bbm_hip_eval_pdf_table(set.tables[k], call_flags, plan->local + o, in_x + o, in_y + o, in_z + o, out_x + o,
+                                  out_y + o, out_z + o, mk, nk, component, unit, at(r), at(g), at(b), at(pdf), stream);
+    if (rc) return rc;
+  }
+  return BBM_HIP_OK;
+}
+
+int bbm_hip_set_sample_eval_sorted(const bbm_hip_set_plan* plan, int call_flags,
+                                   const float* nx, const float* ny, const float* nz,
+                                   const float* tx, const float* ty, const float* tz,
+                                   const float* out_x, const float* out_y, const float* out_z,
+                                   const float* xi0, const float* xi1,
+                                   const uint8_t* mask, size_t slots, uint32_t component, uint32_t unit,
+                                   float* dir_x, float* dir_y, float* dir_z, float* pdf, uint32_t* flag,
+                                   float* r, float* g, float* b, float* wr, float* wg, float* wb, void* stream)
+{
+  (void)unit;
+  bool tangent, done, world;
+  int rc = tangent_arg(tx, ty, tz, tangent);
+  if (rc) return rc;
+  rc = set_sorted_call(plan, call_flags, slots, done);
+  if (rc || done) return rc;
+  if ((rc = set_normal(nx, ny, nz, world))) return rc;
+  if (tangent && !world) return fail(BBM_HIP_ERR_INVALID_ARG, "tangent needs a normal: it fills the frame of the world-space call");
+  SampleEvalArgs checked;
+  if ((rc = sample_eval_args(out_x, out_y, out_z, xi0, xi1, mask, slots, component, dir_x, dir_y, dir_z, pdf, flag,
+                             r, g, b, wr, wg, wb, checked)))
+    return rc;
+  const bbm_hip_set& set = *plan->set;
+  const uint32_t rows = set.rows.rows;
+  for (uint32_t k = 0; k < rows; ++k)
+    if (!set.tables[k]->e->run.sample_eval_tab || (world && !set.tables[k]->e->run.sample_eval_tab_world))
+      return fail(BBM_HIP_ERR_UNSUPPORTED, std::string(set.tables[k]->e->name) + ": no material-table kernels");
+  for (uint32_t k = 0; k < rows; ++k)
+  {
+    const size_t o = plan->seg[k], nk = plan->seg[k + 1] - o;
+    if (nk == 0) continue;
+    const auto in = [o](const float* p) { return p ? p + o : nullptr; };
+    const auto at = [o](float* p) { return p ? p + o : nullptr; };
+    const uint8_t* mk = mask ? mask + o : nullptr;
+    if (world)
+      rc = sample_eval_table_common(true, set.tables[k], call_flags, plan->local + o, nx + o, ny + o, nz + o, in(tx),
+                                    in(ty), in(tz), out_x + o, out_y + o, out_z + o, xi0 + o, xi1 + o, mk, nk,
+                                    component, dir_x + o, dir_y + o, dir_z + o, pdf + o, flag + o, at(r), at(g), at(b),
+                                    at(wr), at(wg), at(wb), stream);
+    else
+      rc = bbm_hip_sample_eval_table(set.tables[k], call_flags, plan->local + o, out_x + o, out_y + o, out_z + o,
+                                     xi0 + o, xi1 + o, mk, nk, component, 0u, dir_x + o, dir_y + o, dir_z + o, pdf + o,
+                                     flag + o, at(r), at(g), at(b), at(wr), at(wg), at(wb), stream);
+    if (rc) return rc;
+  }
+  return BBM_HIP_OK;
 }
 
 // ------------------------------------------------------------------------------- doubleRGB (f64.hip)

@@ -5,6 +5,7 @@
 // exclusive sum of the rows x workgroups counts, and the segment starts rounded up to four), k_set_place (the same
 // rows again, ranked per wave with ballots, the wave totals combined through LDS).  k_set_gather / k_set_scatter move
 // four slots per thread: 16-byte accesses on the sorted side, 4-byte gathers or scatters on the caller's side.
+// k_set_count<true> / k_set_place<true> build the compact plan (§4.21): a lane whose id is out of range is in no slot.
 // Every index read from device memory is compared against its bound before it is used: src[j] against n, a computed
 // slot against the allocated slots.
 #include "set.hpp"
@@ -23,8 +24,10 @@ constexpr uint32_t kWaves = kSetBlock / 64;
 static_assert(kSetBlock == 256 && kWaves == 4 && kSetMaxRows == 32, "the LDS layouts below are written for these");
 
 // The row that owns the global id g and g's index in that row's table; an id past the total (a negative int32
-// included) is row 0's masked-index lane.  rows.off sits in SGPRs: a short scalar compare loop.
-__device__ __forceinline__ uint32_t row_of(const SetRows& rows, uint32_t g, uint32_t& local)
+// included) is row 0's masked-index lane, or (DROP, a compact plan) no lane at all: `valid` is cleared and the lane
+// takes part in no ballot.  rows.off sits in SGPRs: a short scalar compare loop.
+template<bool DROP>
+__device__ __forceinline__ uint32_t row_of(const SetRows& rows, uint32_t g, uint32_t& local, bool& valid)
 {
   uint32_t r = 0, first = 0;
   for (uint32_t k = 1; k < rows.rows; ++k)
@@ -34,6 +37,7 @@ __device__ __forceinline__ uint32_t row_of(const SetRows& rows, uint32_t g, uint
       first = rows.off[k];
     }
   const bool in_range = g < rows.off[rows.rows];
+  if constexpr (DROP) valid = valid && in_range;
   local = in_range ? g - first : kSetNone;
   return in_range ? r : 0u;
 }
@@ -73,6 +77,7 @@ __device__ __forceinline__ uint32_t passes_of(uint32_t n, uint32_t group)
   return left < kSetPasses ? uint32_t(left) : kSetPasses;
 }
 
+template<bool DROP>
 __global__ __launch_bounds__(kSetBlock) void k_set_count(SetPlanArgs a)
 {
   math_tables_init();
@@ -84,9 +89,9 @@ __global__ __launch_bounds__(kSetBlock) void k_set_count(SetPlanArgs a)
   for (uint32_t p = 0; p < passes; ++p)
   {
     const uint64_t i = uint64_t(blockIdx.x) * kSetTile + p * kSetBlock + tid;
-    const bool valid = i < a.n;
+    bool valid = i < a.n;
     uint32_t local;
-    const uint32_t row = valid ? row_of(a.rows, __builtin_nontemporal_load(a.material + i), local) : 0u;
+    const uint32_t row = valid ? row_of<DROP>(a.rows, __builtin_nontemporal_load(a.material + i), local, valid) : 0u;
     wave_rank(valid, row, [&](uint32_t r, uint32_t c) { atomicAdd(&hist[r], c); });
   }
   __syncthreads();
@@ -160,6 +165,7 @@ __global__ __launch_bounds__(kSetBlock) void k_set_scan(SetPlanArgs a)
   }
 }
 
+template<bool DROP>
 __global__ __launch_bounds__(kSetBlock) void k_set_place(SetPlanArgs a)
 {
   math_tables_init();
@@ -177,9 +183,9 @@ __global__ __launch_bounds__(kSetBlock) void k_set_place(SetPlanArgs a)
   {
     __syncthreads();
     const uint64_t i = uint64_t(blockIdx.x) * kSetTile + p * kSetBlock + tid;
-    const bool valid = i < a.n;
+    bool valid = i < a.n;
     uint32_t local = kSetNone;
-    const uint32_t row = valid ? row_of(a.rows, __builtin_nontemporal_load(a.material + i), local) : 0u;
+    const uint32_t row = valid ? row_of<DROP>(a.rows, __builtin_nontemporal_load(a.material + i), local, valid) : 0u;
     const uint32_t rank = wave_rank(valid, row, [&](uint32_t r, uint32_t c) { wave_count[wave][r] = c; });
     __syncthreads();
     if (valid)
@@ -249,6 +255,39 @@ __global__ __launch_bounds__(kSetBlock) void k_set_gather(SetMoveArgs a)
   }
 }
 
+// k_set_gather with every load of the thread (count x 4 values, the mask bytes included) issued before its first
+// store: up to 36 values in flight per thread against four.
+__global__ __launch_bounds__(kSetBlock) void k_set_gather_batched(SetMoveArgs a)
+{
+  math_tables_init();
+  const uint32_t q = blockIdx.x * kSetBlock + threadIdx.x;
+  if (q >= (a.capacity >> 2)) return;
+  const u4 sv = reinterpret_cast<const u4*>(a.src)[q];
+  const uint32_t s[4] = {sv.x, sv.y, sv.z, sv.w};
+  const bool ok[4] = {s[0] < a.n, s[1] < a.n, s[2] < a.n, s[3] < a.n};
+  uint32_t v[kSetMaxIn][4];
+#pragma unroll
+  for (int c = 0; c < kSetMaxIn; ++c)
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+      v[c][j] = (c < a.count && ok[j]) ? __builtin_nontemporal_load(a.from[c] + s[j]) : 0u;
+  uint32_t m = 0;
+  if (a.mask_to)
+  {
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+    {
+      const uint32_t byte = ok[j] ? (a.mask_from ? uint32_t(a.mask_from[s[j]]) : 1u) : 0u;
+      m |= byte << (8 * j);
+    }
+  }
+#pragma unroll
+  for (int c = 0; c < kSetMaxIn; ++c)
+    if (c < a.count)
+      __builtin_nontemporal_store(u4{v[c][0], v[c][1], v[c][2], v[c][3]}, reinterpret_cast<u4*>(a.to[c]) + q);
+  if (a.mask_to) reinterpret_cast<uint32_t*>(a.mask_to)[q] = m;
+}
+
 __global__ __launch_bounds__(kSetBlock) void k_set_scatter(SetMoveArgs a)
 {
   math_tables_init();
@@ -280,9 +319,15 @@ int set_launched(const char* what)
 
 int set_plan_launch(const SetPlanArgs& a, hipStream_t s)
 {
-  hipLaunchKernelGGL(k_set_count, dim3(a.groups), dim3(kSetBlock), 0, s, a);
+  if (a.drop)
+    hipLaunchKernelGGL(k_set_count<true>, dim3(a.groups), dim3(kSetBlock), 0, s, a);
+  else
+    hipLaunchKernelGGL(k_set_count<false>, dim3(a.groups), dim3(kSetBlock), 0, s, a);
   hipLaunchKernelGGL(k_set_scan, dim3(1), dim3(kSetBlock), 0, s, a);
-  hipLaunchKernelGGL(k_set_place, dim3(a.groups), dim3(kSetBlock), 0, s, a);
+  if (a.drop)
+    hipLaunchKernelGGL(k_set_place<true>, dim3(a.groups), dim3(kSetBlock), 0, s, a);
+  else
+    hipLaunchKernelGGL(k_set_place<false>, dim3(a.groups), dim3(kSetBlock), 0, s, a);
   return set_launched("material plan launch failed");
 }
 
@@ -290,6 +335,13 @@ int set_gather_launch(const SetMoveArgs& a, hipStream_t s)
 {
   const unsigned blocks = grid_blocks(a.capacity >> 2, kSetBlock, 0x7fffffffull);
   hipLaunchKernelGGL(k_set_gather, dim3(blocks), dim3(kSetBlock), 0, s, a);
+  return set_launched("material set gather launch failed");
+}
+
+int set_gather_launch_batched(const SetMoveArgs& a, hipStream_t s)
+{
+  const unsigned blocks = grid_blocks(a.capacity >> 2, kSetBlock, 0x7fffffffull);
+  hipLaunchKernelGGL(k_set_gather_batched, dim3(blocks), dim3(kSetBlock), 0, s, a);
   return set_launched("material set gather launch failed");
 }
 

@@ -50,10 +50,11 @@ struct SetPlanArgs
   uint32_t* src;               // slots
   uint32_t* local;             // slots
   uint32_t slots;              // allocated slots of src and local: every computed slot is compared against it
+  uint32_t drop;               // a compact plan: a lane whose id is past the total is in no slot (else row 0's)
 };
 
-// One gather or scatter: `count` four-byte streams between caller arrays of n lanes (4-byte aligned) and sorted
-// arrays of `capacity` slots (16-byte aligned, capacity a multiple of four).
+// One gather or scatter: `count` (at most kSetMaxOut) four-byte streams between caller arrays of n lanes (4-byte
+// aligned) and sorted arrays of `capacity` slots (16-byte aligned, capacity a multiple of four).
 struct SetMoveArgs
 {
   const uint32_t* src;         // capacity slots
@@ -70,5 +71,8 @@ int set_plan_launch(const SetPlanArgs& a, hipStream_t s);
 // Enqueue one gather (lane -> slot; padding slots get zeros and mask 0) or scatter (slot -> lane).
 int set_gather_launch(const SetMoveArgs& a, hipStream_t s);
 int set_scatter_launch(const SetMoveArgs& a, hipStream_t s);
+// The gather in its other shape, for measurement: every load of a thread is issued before its
+// first store.  Same arguments, same result.
+int set_gather_launch_batched(const SetMoveArgs& a, hipStream_t s);
 
 }  // namespace bbmhip

@@ -467,6 +467,71 @@ int bbm_hip_set_sample_eval_tangent(const bbm_hip_set_plan* plan, int call_flags
                                     float* dir_x, float* dir_y, float* dir_z, float* pdf, uint32_t* flag,
                                     float* r, float* g, float* b, float* wr, float* wg, float* wb, void* stream);
 
+/* ---------------------------------------------------------------- material sets in plan order */
+
+/* A renderer whose path state follows its hits permutes that state once per bounce and then shades in place: the set
+ * calls above gather every input and scatter every output on every call; the calls below take streams that already
+ * are in the plan's slot order and run nothing but the table entry points on each table's slice.
+ *
+ * bbm_hip_set_plan_create_compact is bbm_hip_set_plan_create except that a lane whose id is >= the set's total
+ * (0xFFFFFFFF, any negative int32: a terminated path) is in NO slot: it is not counted, not ranked and in no segment.
+ * The order stays stable, segments start at multiples of four slots, padding slots hold src = 0xFFFFFFFF, and create
+ * waits for the stream once.  bbm_hip_set_plan_lanes is still n; bbm_hip_set_plan_capacity may be far below n (0 where
+ * every id is out of range).  The lane-order calls (bbm_hip_set_eval_pdf, bbm_hip_set_sample_eval and their _tangent
+ * forms) refuse a compact plan with BBM_HIP_ERR_INVALID_ARG before anything is allocated or launched: their scatter
+ * would leave the dropped lanes' outputs unwritten.  bbm_hip_set_plan_compact: 1 / 0, negative for NULL.
+ *
+ * bbm_hip_set_plan_gather / _scatter move `count` streams of FOUR-BYTE elements (float, int32, uint32: bits are
+ * moved, nothing is converted) between lane order (n elements each, 4-byte aligned) and slot order (`capacity`
+ * elements each, 16-byte aligned).  from and to are HOST arrays of count DEVICE pointers; count may be any number
+ * >= 0 (the library issues as many launches as it needs).  from and to must not overlap.
+ *   gather:  to[c][j] = from[c][src[j]] for every slot j with src[j] < n, 0 in a padding slot.  mask_to (optional,
+ *            capacity bytes, 4-byte aligned) gets 0 in a padding slot and mask_from[src[j]] in a real one, or 1 where
+ *            mask_from is NULL; mask_from without mask_to is an error.
+ *   scatter: to[c][src[j]] = from[c][j] for every slot j with src[j] < n.  A lane that is in no slot (a compact plan
+ *            has such lanes) is not written.
+ * BBM_HIP_ERR_INVALID_ARG ahead of any launch: a negative count, NULL from or to with count > 0, a NULL plan, another
+ * n than the plan's, a NULL entry, a slot-order array that is not 16-byte aligned.  A plan without slots (n == 0, or
+ * a compact plan whose ids are all out of range) is BBM_HIP_OK with nothing launched and no entry looked at, and so
+ * is count == 0 with no mask.  bbm_hip_set_gather_shape selects how the gather issues its loads
+ * (0, the default: a stream at a time; 1: all of a thread's loads before its first store), process-wide, and returns
+ * the previous setting: the results are the same, the switch exists for measurement.
+ *
+ * bbm_hip_set_eval_pdf_sorted / bbm_hip_set_sample_eval_sorted: every array is in slot order and holds `capacity`
+ * elements; slots must equal bbm_hip_set_plan_capacity(plan).  No scratch, no launch but the table entry points: for
+ * every table k with a non-empty segment [seg[k], seg[k + 1]) the matching table call runs on that slice of the
+ * caller's arrays with the plan's local indices.  Slot j with src[j] = i returns, bit for bit, what the lane-order set
+ * call returns for lane i when lane i's inputs and mask byte stand in slot j.  A padding slot is the table's
+ * out-of-range-index lane at whatever inputs the slot holds (zeros after bbm_hip_set_plan_gather); its outputs are
+ * written and mean nothing.  A NULL mask stays NULL.  Normal and tangent pointers, the output groups and every check
+ * are those of bbm_hip_set_eval_pdf_tangent / bbm_hip_set_sample_eval_tangent, in their order (tangent and normal
+ * all three NULL or all three set; the tangent and cos_in need the normal).  Compact and plain plans alike; an empty
+ * plan is BBM_HIP_OK.  With 16-byte aligned arrays every slice is aligned and takes the quad kernels; other
+ * alignments take the one-lane kernels, as for any table call.  Outputs must not alias inputs. */
+int bbm_hip_set_plan_create_compact(const bbm_hip_set* set, const uint32_t* material, size_t n, void* stream,
+                                    bbm_hip_set_plan** out);
+int bbm_hip_set_plan_compact(const bbm_hip_set_plan* plan);
+int bbm_hip_set_plan_gather(const bbm_hip_set_plan* plan, const void* const* from, void* const* to, int count,
+                            const uint8_t* mask_from, uint8_t* mask_to, size_t n, void* stream);
+int bbm_hip_set_plan_scatter(const bbm_hip_set_plan* plan, const void* const* from, void* const* to, int count,
+                             size_t n, void* stream);
+int bbm_hip_set_gather_shape(int shape);
+int bbm_hip_set_eval_pdf_sorted(const bbm_hip_set_plan* plan, int call_flags,
+                                const float* nx, const float* ny, const float* nz,
+                                const float* tx, const float* ty, const float* tz,
+                                const float* in_x, const float* in_y, const float* in_z,
+                                const float* out_x, const float* out_y, const float* out_z,
+                                const uint8_t* mask, size_t slots, uint32_t component, uint32_t unit,
+                                float* r, float* g, float* b, float* pdf, float* cos_in, void* stream);
+int bbm_hip_set_sample_eval_sorted(const bbm_hip_set_plan* plan, int call_flags,
+                                   const float* nx, const float* ny, const float* nz,
+                                   const float* tx, const float* ty, const float* tz,
+                                   const float* out_x, const float* out_y, const float* out_z,
+                                   const float* xi0, const float* xi1,
+                                   const uint8_t* mask, size_t slots, uint32_t component, uint32_t unit,
+                                   float* dir_x, float* dir_y, float* dir_z, float* pdf, uint32_t* flag,
+                                   float* r, float* g, float* b, float* wr, float* wg, float* wb, void* stream);
+
 /* ---------------------------------------------------------------- doubleRGB (Value = double) */
 
 /* The reference's doubleRGB configuration (backbone/native/include/backbone.h:41-42: Value = double, Spectrum =
