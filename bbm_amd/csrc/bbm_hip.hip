@@ -1009,64 +1009,143 @@ struct bbm_hip_set_plan
 
 namespace {
 
-// What the two calls on a plan check first; *done is set where nothing is left to do (n == 0).
-int set_call(const bbm_hip_set_plan* p, int call_flags, size_t n, bool& done)
-{
-  done = false;
-  if (!p) return fail(BBM_HIP_ERR_INVALID_ARG, "plan is NULL");
-  if (const int rc = table_call(p->set->tables[0], call_flags, 0, nullptr)) return rc;
-  if (n != p->n)
-    return fail(BBM_HIP_ERR_INVALID_ARG, "n is " + std::to_string(n) + ", the plan was made for " + std::to_string(p->n) + " lanes");
-  done = n == 0;
-  return BBM_HIP_OK;
-}
+// The streams of a call, in lane order or in slot order.  tan: tx, ty, tz, all or none.  in: nx, ny, nz (all: the world
+// call; none: the local call), then in and out (eval + pdf) or out, xi0 and xi1 (sample_eval).  res: r, g, b, pdf and
+// cos_in, or dir, pdf, flag (a four-byte stream like the rest), r, g, b, wr, wg and wb.
 
-// The lane-order calls scatter through src, which would leave a dropped lane's outputs unwritten.
-int set_lane_order(const bbm_hip_set_plan* p)
+// What every call on a plan checks first, in this order: the tangent's mixture, the plan, the call flags, the length,
+// the normal's mixture, a tangent without a normal.  lanes: a call in lane order, whose `count` is the plan's n and
+// which refuses a compact plan before anything else about it (it scatters through src, which would leave a dropped
+// lane's outputs unwritten); otherwise a call in plan order, whose `count` is the plan's capacity.  done: nothing is
+// left to do (no lane, no slot), found before any stream but the tangent is looked at.
+int set_call(const bbm_hip_set_plan* p, bool lanes, int call_flags, size_t count, const float* const* tan,
+             const float* const* in, bool& world, bool& done)
 {
-  if (p && p->compact)
+  bool tangent;
+  done = world = false;
+  if (const int rc = tangent_arg(tan[0], tan[1], tan[2], tangent)) return rc;
+  if (lanes && p && p->compact)
     return fail(BBM_HIP_ERR_INVALID_ARG, "a compact plan leaves lanes out: use the calls in plan order (the *_sorted calls)");
-  return BBM_HIP_OK;
-}
-
-// What the two calls in plan order check first: set_call's checks with the slots in place of the lanes.
-int set_sorted_call(const bbm_hip_set_plan* p, int call_flags, size_t slots, bool& done)
-{
-  done = false;
   if (!p) return fail(BBM_HIP_ERR_INVALID_ARG, "plan is NULL");
   if (const int rc = table_call(p->set->tables[0], call_flags, 0, nullptr)) return rc;
-  const size_t capacity = p->seg[p->set->rows.rows];
-  if (slots != capacity)
-    return fail(BBM_HIP_ERR_INVALID_ARG, "slots is " + std::to_string(slots) + ", the plan's capacity is " + std::to_string(capacity));
-  done = capacity == 0;
+  const size_t have = lanes ? p->n : p->seg[p->set->rows.rows];
+  if (count != have)
+    return fail(BBM_HIP_ERR_INVALID_ARG,
+                lanes ? "n is " + std::to_string(count) + ", the plan was made for " + std::to_string(have) + " lanes"
+                      : "slots is " + std::to_string(count) + ", the plan's capacity is " + std::to_string(have));
+  if ((done = have == 0)) return BBM_HIP_OK;
+  world = in[0] && in[1] && in[2];
+  if (!world && (in[0] || in[1] || in[2])) return fail(BBM_HIP_ERR_INVALID_ARG, "normal: give nx, ny and nz or none");
+  if (tangent && !world) return fail(BBM_HIP_ERR_INVALID_ARG, "tangent needs a normal: it fills the frame of the world-space call");
   return BBM_HIP_OK;
 }
 
-// all three normal pointers (the world call), none (the local call); a mixture is an error
-int set_normal(const float* nx, const float* ny, const float* nz, bool& world)
+// Everything eval + pdf checks before its first launch, in either order.
+int set_eval_pdf_check(const bbm_hip_set_plan* p, bool lanes, int call_flags, const float* const* tan,
+                       const float* const* in, const uint8_t* mask, size_t count, uint32_t component,
+                       float* const* res, bool& world, bool& done)
 {
-  world = nx && ny && nz;
-  if (!world && (nx || ny || nz)) return fail(BBM_HIP_ERR_INVALID_ARG, "normal: give nx, ny and nz or none");
+  int rc = set_call(p, lanes, call_flags, count, tan, in, world, done);
+  if (rc || done) return rc;
+  if (res[4] && !world) return fail(BBM_HIP_ERR_INVALID_ARG, "cos_in needs a normal: it is the cosine of `in` against it");
+  EvalArgs checked;
+  int mode = 0;
+  if ((rc = eval_args(mode, in[3], in[4], in[5], in[6], in[7], in[8], mask, count, component, res[0], res[1], res[2],
+                      res[3], checked)))
+    return rc;
+  for (const bbm_hip_table* t : p->set->tables)
+    if (world && !t->e->run.eval_pdf_tab_world)
+      return fail(BBM_HIP_ERR_UNSUPPORTED, std::string(t->e->name) + ": no material-table kernels");
   return BBM_HIP_OK;
 }
 
-// The sorted buffers of one call: `streams` arrays of capacity four-byte slots and the mask bytes, one scratch block.
-struct SetScratch
+// The same for sample_eval.
+int set_sample_eval_check(const bbm_hip_set_plan* p, bool lanes, int call_flags, const float* const* tan,
+                          const float* const* in, const uint8_t* mask, size_t count, uint32_t component,
+                          float* const* res, bool& world, bool& done)
 {
-  char* base = nullptr;
-  size_t used = 0, stride = 0;
-  hipStream_t s = nullptr;
-  int acquire(uint32_t capacity, int streams, bool mask, hipStream_t stream)
+  int rc = set_call(p, lanes, call_flags, count, tan, in, world, done);
+  if (rc || done) return rc;
+  SampleEvalArgs checked;
+  if ((rc = sample_eval_args(in[3], in[4], in[5], in[6], in[7], mask, count, component, res[0], res[1], res[2], res[3],
+                             reinterpret_cast<uint32_t*>(res[4]), res[5], res[6], res[7], res[8], res[9], res[10],
+                             checked)))
+    return rc;
+  for (const bbm_hip_table* t : p->set->tables)
+    if (!t->e->run.sample_eval_tab || (world && !t->e->run.sample_eval_tab_world))
+      return fail(BBM_HIP_ERR_UNSUPPORTED, std::string(t->e->name) + ": no material-table kernels");
+  return BBM_HIP_OK;
+}
+
+// slot o of a stream in slot order; a stream that is not given stays NULL
+template<class T> T* at(T* p, size_t o) { return p ? p + o : nullptr; }
+
+// The row loop of a call kind: the table call on every segment of the plan that has slots.  The streams are in slot
+// order: the caller's own (the *_sorted calls) or the scratch of a call in lane order (set_lane_order).
+using SetRowLoop = int(const bbm_hip_set_plan& plan, int call_flags, bool world, const float* const* tan,
+                       const float* const* in, const uint8_t* mask, uint32_t component, uint32_t unit,
+                       float* const* res, void* stream);
+
+int set_eval_pdf_rows(const bbm_hip_set_plan& plan, int call_flags, bool world, const float* const* tan,
+                      const float* const* in, const uint8_t* mask, uint32_t component, uint32_t unit,
+                      float* const* res, void* stream)
+{
+  for (uint32_t k = 0; k < plan.set->rows.rows; ++k)
   {
-    s = stream;
-    stride = size_t(capacity) * 4u;
-    base = static_cast<char*>(scratch_acquire(stride * size_t(streams) + (mask ? capacity : 0u), s));
-    return base ? BBM_HIP_OK : fail(BBM_HIP_ERR_HIP, "material set scratch: " + scratch_failure());
+    const size_t o = plan.seg[k], nk = plan.seg[k + 1] - o;
+    if (nk == 0) continue;
+    const bbm_hip_table* t = plan.set->tables[k];
+    const float *tk[3], *i[9];
+    float* r[5];
+    for (int c = 0; c < 3; ++c) tk[c] = at(tan[c], o);
+    for (int c = 0; c < 9; ++c) i[c] = at(in[c], o);
+    for (int c = 0; c < 5; ++c) r[c] = at(res[c], o);
+    const int rc =
+        world ? eval_pdf_table_world_common(t, call_flags, plan.local + o, i[0], i[1], i[2], tk[0], tk[1], tk[2], i[3],
+                                            i[4], i[5], i[6], i[7], i[8], at(mask, o), nk, component, r[0], r[1], r[2],
+                                            r[3], r[4], stream)
+              : bbm_hip_eval_pdf_table(t, call_flags, plan.local + o, i[3], i[4], i[5], i[6], i[7], i[8], at(mask, o),
+                                       nk, component, unit, r[0], r[1], r[2], r[3], stream);
+    if (rc) return rc;
   }
-  template<class T> T* take(size_t bytes) { T* p = reinterpret_cast<T*>(base + used); used += bytes; return p; }
-  float* stream4() { return take<float>(stride); }
-  ~SetScratch() { if (base) scratch_release(base, s); }
-};
+  return BBM_HIP_OK;
+}
+
+int set_sample_eval_rows(const bbm_hip_set_plan& plan, int call_flags, bool world, const float* const* tan,
+                         const float* const* in, const uint8_t* mask, uint32_t component, uint32_t,
+                         float* const* res, void* stream)
+{
+  for (uint32_t k = 0; k < plan.set->rows.rows; ++k)
+  {
+    const size_t o = plan.seg[k], nk = plan.seg[k + 1] - o;
+    if (nk == 0) continue;
+    const bbm_hip_table* t = plan.set->tables[k];
+    const float *tk[3], *i[8];
+    float* r[11];
+    for (int c = 0; c < 3; ++c) tk[c] = at(tan[c], o);
+    for (int c = 0; c < 8; ++c) i[c] = at(in[c], o);
+    for (int c = 0; c < 11; ++c) r[c] = at(res[c], o);
+    uint32_t* flag = reinterpret_cast<uint32_t*>(r[4]);
+    const int rc =
+        world ? sample_eval_table_common(true, t, call_flags, plan.local + o, i[0], i[1], i[2], tk[0], tk[1], tk[2],
+                                         i[3], i[4], i[5], i[6], i[7], at(mask, o), nk, component, r[0], r[1], r[2],
+                                         r[3], flag, r[5], r[6], r[7], r[8], r[9], r[10], stream)
+              : bbm_hip_sample_eval_table(t, call_flags, plan.local + o, i[3], i[4], i[5], i[6], i[7], at(mask, o), nk,
+                                          component, 0u, r[0], r[1], r[2], r[3], flag, r[5], r[6], r[7], r[8], r[9],
+                                          r[10], stream);
+    if (rc) return rc;
+  }
+  return BBM_HIP_OK;
+}
+
+// a plan's move with no stream in it yet
+SetMoveArgs set_move(const bbm_hip_set_plan& p)
+{
+  SetMoveArgs m;
+  std::memset(&m, 0, sizeof(m));
+  m.src = p.src; m.n = p.n; m.capacity = p.seg[p.set->rows.rows];
+  return m;
+}
 
 // a caller stream and its sorted twin, entered into a gather (lane -> slot) or a scatter (slot -> lane)
 void move_in(SetMoveArgs& m, const void* lanes, void* sorted)
@@ -1080,7 +1159,46 @@ void move_out(SetMoveArgs& m, void* sorted, void* lanes)
   m.to[m.count++] = static_cast<uint32_t*>(lanes);
 }
 
-// whether a row of the set reads a tangent (bbm_hip_model_anisotropic); without one the tangent is not gathered
+// The sorted buffers of a call in lane order: `streams` arrays of capacity four-byte slots and the mask bytes, one
+// scratch block.  A take past the block yields NULL and makes status() an error, which the call returns before its
+// first launch: a count that disagrees with the takes never becomes a write outside the block.
+struct SetScratch
+{
+  char* base = nullptr;
+  size_t used = 0, size = 0, stride = 0;
+  hipStream_t s = nullptr;
+  int acquire(uint32_t capacity, int streams, bool mask, hipStream_t stream)
+  {
+    s = stream;
+    stride = size_t(capacity) * 4u;
+    size = stride * size_t(streams) + (mask ? capacity : 0u);
+    base = static_cast<char*>(scratch_acquire(size, s));
+    return base ? BBM_HIP_OK : fail(BBM_HIP_ERR_HIP, "material set scratch: " + scratch_failure());
+  }
+  template<class T> T* take(size_t bytes)
+  {
+    T* p = used + bytes <= size ? reinterpret_cast<T*>(base + used) : nullptr;
+    used += bytes;
+    return p;
+  }
+  // The sorted twins of the streams of lanes[] that are given, which a move holds in this order: each goes to the
+  // move's slot-order `side` (a gather's to, a scatter's from) and to slot[c], which is NULL where lanes[c] is.
+  template<class L, class P> void twins(L* const* lanes, int count, P* side, float** slot)
+  {
+    for (int c = 0, j = 0; c < count; ++c)
+    {
+      slot[c] = lanes[c] ? take<float>(stride) : nullptr;
+      if (lanes[c]) side[j++] = reinterpret_cast<uint32_t*>(slot[c]);
+    }
+  }
+  int status() const
+  {
+    return used <= size ? BBM_HIP_OK : fail(BBM_HIP_ERR_HIP, "material set scratch: more streams taken than entered");
+  }
+  ~SetScratch() { if (base) scratch_release(base, s); }
+};
+
+// whether a row of the set reads a tangent (bbm_hip_model_anisotropic)
 bool set_any_anisotropic(const bbm_hip_set& set)
 {
   for (const bbm_hip_table* t : set.tables)
@@ -1088,15 +1206,39 @@ bool set_any_anisotropic(const bbm_hip_set& set)
   return false;
 }
 
-// The tangent's gather, a launch of its own beside `in`'s (k_set_gather carries kSetMaxIn streams, which the normal,
-// `in` and `out` fill): the same order and slots, no mask.
-void set_tangent_streams(SetMoveArgs& tan_in, const SetMoveArgs& in, const float* tx, const float* ty, const float* tz,
-                         float** sorted, SetScratch& scratch)
+// A call in lane order: the call in plan order, `rows`, between a gather of the nin + 3 input
+// streams into scratch and a scatter of the nout output streams out of it.  The streams that are given enter the
+// moves, which counts them; the block is acquired for that many, and their twins are then taken from it in the order
+// of entry: gathered, scattered, tangent, mask.
+int set_lane_order(SetRowLoop* rows, const bbm_hip_set_plan& plan, int call_flags, bool world, const float* const* tan,
+                   const float* const* lanes, int nin, const uint8_t* mask, uint32_t component, uint32_t unit,
+                   float* const* res, int nout, void* stream)
 {
-  std::memset(&tan_in, 0, sizeof(tan_in));
-  tan_in.src = in.src; tan_in.n = in.n; tan_in.capacity = in.capacity;
-  const float* lanes[3] = {tx, ty, tz};
-  for (int c = 0; c < 3; ++c) move_in(tan_in, lanes[c], sorted[c] = scratch.stream4());
+  const hipStream_t s = static_cast<hipStream_t>(stream);
+  // The tangent's gather is a launch of its own (k_set_gather carries kSetMaxIn streams, which normal, in and out
+  // fill); without an anisotropic row the tangent is neither gathered nor passed on.
+  const float* const none[3] = {};
+  if (!set_any_anisotropic(*plan.set)) tan = none;
+  SetMoveArgs in = set_move(plan), out = in, tan_in = in;
+  for (int c = 0; c < nin; ++c)
+    if (lanes[c]) move_in(in, lanes[c], nullptr);
+  for (int c = 0; c < nout; ++c)
+    if (res[c]) move_out(out, nullptr, res[c]);
+  for (int c = 0; c < 3; ++c)
+    if (tan[c]) move_in(tan_in, tan[c], nullptr);
+  SetScratch scratch;
+  int rc = scratch.acquire(in.capacity, in.count + out.count + tan_in.count, mask != nullptr, s);
+  if (rc) return rc;
+  float *sorted[kSetMaxIn], *sres[kSetMaxOut], *stan[3];
+  scratch.twins(lanes, nin, in.to, sorted);
+  scratch.twins(res, nout, out.from, sres);
+  scratch.twins(tan, 3, tan_in.to, stan);
+  in.mask_from = mask;
+  in.mask_to = mask ? scratch.take<uint8_t>(in.capacity) : nullptr;
+  if ((rc = scratch.status()) || (rc = set_gather_launch(in, s))) return rc;
+  if (tan_in.count && (rc = set_gather_launch(tan_in, s))) return rc;
+  if ((rc = rows(plan, call_flags, world, stan, sorted, in.mask_to, component, unit, sres, stream))) return rc;
+  return set_scatter_launch(out, s);
 }
 
 }  // namespace
@@ -1268,74 +1410,24 @@ int bbm_hip_set_plan_segments(const bbm_hip_set_plan* plan, uint64_t* out, uint3
 
 const uint32_t* bbm_hip_set_plan_order(const bbm_hip_set_plan* plan) { return plan ? plan->src : nullptr; }
 
-// tx, ty, tz: all set (bbm_hip_set_eval_pdf_tangent) or all NULL
-static int set_eval_pdf_common(const bbm_hip_set_plan* plan, int call_flags,
+// The three eval + pdf calls on a plan.  lanes: in lane order, `count` lanes; otherwise in plan order, `count` slots.
+// tx, ty, tz: all set or all NULL (the call without _tangent).
+static int set_eval_pdf_common(bool lanes, const bbm_hip_set_plan* plan, int call_flags,
                                const float* nx, const float* ny, const float* nz,
                                const float* tx, const float* ty, const float* tz,
                                const float* in_x, const float* in_y, const float* in_z,
                                const float* out_x, const float* out_y, const float* out_z,
-                               const uint8_t* mask, size_t n, uint32_t component, uint32_t unit,
+                               const uint8_t* mask, size_t count, uint32_t component, uint32_t unit,
                                float* r, float* g, float* b, float* pdf, float* cos_in, void* stream)
 {
-  bool done, world;
-  int rc = set_lane_order(plan);
-  if (rc) return rc;
-  rc = set_call(plan, call_flags, n, done);
-  if (rc || done) return rc;
-  if ((rc = set_normal(nx, ny, nz, world))) return rc;
-  if (tx && !world) return fail(BBM_HIP_ERR_INVALID_ARG, "tangent needs a normal: it fills the frame of the world-space call");
-  if (cos_in && !world) return fail(BBM_HIP_ERR_INVALID_ARG, "cos_in needs a normal: it is the cosine of `in` against it");
-  EvalArgs checked;
-  int mode = 0;
-  if ((rc = eval_args(mode, in_x, in_y, in_z, out_x, out_y, out_z, mask, n, component, r, g, b, pdf, checked))) return rc;
-  const bbm_hip_set& set = *plan->set;
-  const uint32_t rows = set.rows.rows, capacity = plan->seg[rows];
-  for (uint32_t k = 0; world && k < rows; ++k)
-    if (!set.tables[k]->e->run.eval_pdf_tab_world)
-      return fail(BBM_HIP_ERR_UNSUPPORTED, std::string(set.tables[k]->e->name) + ": no material-table kernels");
-  const hipStream_t s = static_cast<hipStream_t>(stream);
-  const bool eval = mode & kModeEval, want_pdf = mode & kModePdf;
-  SetScratch scratch;
-  const bool tangent = tx && set_any_anisotropic(set);
-  if ((rc = scratch.acquire(capacity, (world ? 9 : 6) + (tangent ? 3 : 0) + (eval ? 3 : 0) + (want_pdf ? 1 : 0) +
-                                          (cos_in ? 1 : 0), mask != nullptr, s)))
-    return rc;
-  SetMoveArgs in, out, tan_in;
-  std::memset(&in, 0, sizeof(in));
-  in.src = plan->src; in.n = plan->n; in.capacity = capacity;
-  out = in;
-  const float* lanes[9] = {nx, ny, nz, in_x, in_y, in_z, out_x, out_y, out_z};
-  float* sorted[9] = {};
-  for (int c = world ? 0 : 3; c < 9; ++c) move_in(in, lanes[c], sorted[c] = scratch.stream4());
+  const float* tan[3] = {tx, ty, tz};
+  const float* in[9] = {nx, ny, nz, in_x, in_y, in_z, out_x, out_y, out_z};
   float* res[5] = {r, g, b, pdf, cos_in};
-  float* sres[5] = {};
-  for (int c = 0; c < 5; ++c)
-    if (res[c]) move_out(out, sres[c] = scratch.stream4(), res[c]);
-  float* stan[3] = {};
-  if (tangent) set_tangent_streams(tan_in, in, tx, ty, tz, stan, scratch);
-  uint8_t* smask = mask ? scratch.take<uint8_t>(capacity) : nullptr;
-  in.mask_from = mask; in.mask_to = smask;
-  if ((rc = set_gather_launch(in, s))) return rc;
-  if (tangent && (rc = set_gather_launch(tan_in, s))) return rc;
-  for (uint32_t k = 0; k < rows; ++k)
-  {
-    const size_t o = plan->seg[k], nk = plan->seg[k + 1] - o;
-    if (nk == 0) continue;
-    const auto at = [o](float* p) { return p ? p + o : nullptr; };
-    const uint8_t* mk = smask ? smask + o : nullptr;
-    if (world)
-      rc = eval_pdf_table_world_common(set.tables[k], call_flags, plan->local + o, sorted[0] + o, sorted[1] + o,
-                                       sorted[2] + o, at(stan[0]), at(stan[1]), at(stan[2]), sorted[3] + o,
-                                       sorted[4] + o, sorted[5] + o, sorted[6] + o, sorted[7] + o, sorted[8] + o, mk,
-                                       nk, component, at(sres[0]), at(sres[1]), at(sres[2]), at(sres[3]), at(sres[4]),
-                                       stream);
-    else
-      rc = bbm_hip_eval_pdf_table(set.tables[k], call_flags, plan->local + o, sorted[3] + o, sorted[4] + o,
-                                  sorted[5] + o, sorted[6] + o, sorted[7] + o, sorted[8] + o, mk, nk, component, unit,
-                                  at(sres[0]), at(sres[1]), at(sres[2]), at(sres[3]), stream);
-    if (rc) return rc;
-  }
-  return set_scatter_launch(out, s);
+  bool world, done;
+  const int rc = set_eval_pdf_check(plan, lanes, call_flags, tan, in, mask, count, component, res, world, done);
+  if (rc || done) return rc;
+  if (!lanes) return set_eval_pdf_rows(*plan, call_flags, world, tan, in, mask, component, unit, res, stream);
+  return set_lane_order(set_eval_pdf_rows, *plan, call_flags, world, tan, in, 9, mask, component, unit, res, 5, stream);
 }
 
 int bbm_hip_set_eval_pdf(const bbm_hip_set_plan* plan, int call_flags,
@@ -1345,8 +1437,8 @@ int bbm_hip_set_eval_pdf(const bbm_hip_set_plan* plan, int call_flags,
                          const uint8_t* mask, size_t n, uint32_t component, uint32_t unit,
                          float* r, float* g, float* b, float* pdf, float* cos_in, void* stream)
 {
-  return set_eval_pdf_common(plan, call_flags, nx, ny, nz, nullptr, nullptr, nullptr, in_x, in_y, in_z, out_x, out_y,
-                             out_z, mask, n, component, unit, r, g, b, pdf, cos_in, stream);
+  return set_eval_pdf_common(true, plan, call_flags, nx, ny, nz, nullptr, nullptr, nullptr, in_x, in_y, in_z, out_x,
+                             out_y, out_z, mask, n, component, unit, r, g, b, pdf, cos_in, stream);
 }
 
 int bbm_hip_set_eval_pdf_tangent(const bbm_hip_set_plan* plan, int call_flags,
@@ -1357,81 +1449,28 @@ int bbm_hip_set_eval_pdf_tangent(const bbm_hip_set_plan* plan, int call_flags,
                                  const uint8_t* mask, size_t n, uint32_t component, uint32_t unit,
                                  float* r, float* g, float* b, float* pdf, float* cos_in, void* stream)
 {
-  bool tangent;
-  if (const int rc = tangent_arg(tx, ty, tz, tangent)) return rc;
-  return set_eval_pdf_common(plan, call_flags, nx, ny, nz, tx, ty, tz, in_x, in_y, in_z, out_x, out_y, out_z, mask, n,
-                             component, unit, r, g, b, pdf, cos_in, stream);
+  return set_eval_pdf_common(true, plan, call_flags, nx, ny, nz, tx, ty, tz, in_x, in_y, in_z, out_x, out_y, out_z,
+                             mask, n, component, unit, r, g, b, pdf, cos_in, stream);
 }
 
-static int set_sample_eval_common(const bbm_hip_set_plan* plan, int call_flags,
+// The three sample_eval calls on a plan, on the same terms.
+static int set_sample_eval_common(bool lanes, const bbm_hip_set_plan* plan, int call_flags,
                                   const float* nx, const float* ny, const float* nz,
                                   const float* tx, const float* ty, const float* tz,
                                   const float* out_x, const float* out_y, const float* out_z,
                                   const float* xi0, const float* xi1,
-                                  const uint8_t* mask, size_t n, uint32_t component,
+                                  const uint8_t* mask, size_t count, uint32_t component,
                                   float* dir_x, float* dir_y, float* dir_z, float* pdf, uint32_t* flag,
                                   float* r, float* g, float* b, float* wr, float* wg, float* wb, void* stream)
 {
-  bool done, world;
-  int rc = set_lane_order(plan);
-  if (rc) return rc;
-  rc = set_call(plan, call_flags, n, done);
+  const float* tan[3] = {tx, ty, tz};
+  const float* in[8] = {nx, ny, nz, out_x, out_y, out_z, xi0, xi1};
+  float* res[11] = {dir_x, dir_y, dir_z, pdf, reinterpret_cast<float*>(flag), r, g, b, wr, wg, wb};
+  bool world, done;
+  const int rc = set_sample_eval_check(plan, lanes, call_flags, tan, in, mask, count, component, res, world, done);
   if (rc || done) return rc;
-  if ((rc = set_normal(nx, ny, nz, world))) return rc;
-  if (tx && !world) return fail(BBM_HIP_ERR_INVALID_ARG, "tangent needs a normal: it fills the frame of the world-space call");
-  SampleEvalArgs checked;
-  if ((rc = sample_eval_args(out_x, out_y, out_z, xi0, xi1, mask, n, component, dir_x, dir_y, dir_z, pdf, flag,
-                             r, g, b, wr, wg, wb, checked)))
-    return rc;
-  const bbm_hip_set& set = *plan->set;
-  const uint32_t rows = set.rows.rows, capacity = plan->seg[rows];
-  for (uint32_t k = 0; k < rows; ++k)
-    if (!set.tables[k]->e->run.sample_eval_tab || (world && !set.tables[k]->e->run.sample_eval_tab_world))
-      return fail(BBM_HIP_ERR_UNSUPPORTED, std::string(set.tables[k]->e->name) + ": no material-table kernels");
-  const hipStream_t s = static_cast<hipStream_t>(stream);
-  SetScratch scratch;
-  const bool tangent = tx && set_any_anisotropic(set);
-  if ((rc = scratch.acquire(capacity, (world ? 8 : 5) + (tangent ? 3 : 0) + 5 + (r ? 3 : 0) + (wr ? 3 : 0),
-                            mask != nullptr, s)))
-    return rc;
-  SetMoveArgs in, out, tan_in;
-  std::memset(&in, 0, sizeof(in));
-  in.src = plan->src; in.n = plan->n; in.capacity = capacity;
-  out = in;
-  const float* lanes[8] = {nx, ny, nz, out_x, out_y, out_z, xi0, xi1};
-  float* sorted[8] = {};
-  for (int c = world ? 0 : 3; c < 8; ++c) move_in(in, lanes[c], sorted[c] = scratch.stream4());
-  void* res[11] = {dir_x, dir_y, dir_z, pdf, flag, r, g, b, wr, wg, wb};
-  float* sres[11] = {};
-  for (int c = 0; c < 11; ++c)
-    if (res[c]) move_out(out, sres[c] = scratch.stream4(), res[c]);
-  float* stan[3] = {};
-  if (tangent) set_tangent_streams(tan_in, in, tx, ty, tz, stan, scratch);
-  uint8_t* smask = mask ? scratch.take<uint8_t>(capacity) : nullptr;
-  in.mask_from = mask; in.mask_to = smask;
-  if ((rc = set_gather_launch(in, s))) return rc;
-  if (tangent && (rc = set_gather_launch(tan_in, s))) return rc;
-  for (uint32_t k = 0; k < rows; ++k)
-  {
-    const size_t o = plan->seg[k], nk = plan->seg[k + 1] - o;
-    if (nk == 0) continue;
-    const auto at = [o](float* p) { return p ? p + o : nullptr; };
-    const uint8_t* mk = smask ? smask + o : nullptr;
-    uint32_t* fl = reinterpret_cast<uint32_t*>(sres[4]) + o;
-    if (world)
-      rc = sample_eval_table_common(true, set.tables[k], call_flags, plan->local + o, sorted[0] + o, sorted[1] + o,
-                                    sorted[2] + o, at(stan[0]), at(stan[1]), at(stan[2]), sorted[3] + o, sorted[4] + o,
-                                    sorted[5] + o, sorted[6] + o, sorted[7] + o, mk, nk, component, at(sres[0]),
-                                    at(sres[1]), at(sres[2]), at(sres[3]), fl, at(sres[5]), at(sres[6]), at(sres[7]),
-                                    at(sres[8]), at(sres[9]), at(sres[10]), stream);
-    else
-      rc = bbm_hip_sample_eval_table(set.tables[k], call_flags, plan->local + o, sorted[3] + o, sorted[4] + o,
-                                     sorted[5] + o, sorted[6] + o, sorted[7] + o, mk, nk, component, 0u, at(sres[0]),
-                                     at(sres[1]), at(sres[2]), at(sres[3]), fl, at(sres[5]), at(sres[6]), at(sres[7]),
-                                     at(sres[8]), at(sres[9]), at(sres[10]), stream);
-    if (rc) return rc;
-  }
-  return set_scatter_launch(out, s);
+  if (!lanes) return set_sample_eval_rows(*plan, call_flags, world, tan, in, mask, component, 0u, res, stream);
+  return set_lane_order(set_sample_eval_rows, *plan, call_flags, world, tan, in, 8, mask, component, 0u, res, 11, stream);
 }
 
 int bbm_hip_set_sample_eval(const bbm_hip_set_plan* plan, int call_flags,
@@ -1443,8 +1482,8 @@ int bbm_hip_set_sample_eval(const bbm_hip_set_plan* plan, int call_flags,
                             float* r, float* g, float* b, float* wr, float* wg, float* wb, void* stream)
 {
   (void)unit;
-  return set_sample_eval_common(plan, call_flags, nx, ny, nz, nullptr, nullptr, nullptr, out_x, out_y, out_z, xi0, xi1,
-                                mask, n, component, dir_x, dir_y, dir_z, pdf, flag, r, g, b, wr, wg, wb, stream);
+  return set_sample_eval_common(true, plan, call_flags, nx, ny, nz, nullptr, nullptr, nullptr, out_x, out_y, out_z, xi0,
+                                xi1, mask, n, component, dir_x, dir_y, dir_z, pdf, flag, r, g, b, wr, wg, wb, stream);
 }
 
 int bbm_hip_set_sample_eval_tangent(const bbm_hip_set_plan* plan, int call_flags,
@@ -1457,9 +1496,7 @@ int bbm_hip_set_sample_eval_tangent(const bbm_hip_set_plan* plan, int call_flags
                                     float* r, float* g, float* b, float* wr, float* wg, float* wb, void* stream)
 {
   (void)unit;
-  bool tangent;
-  if (const int rc = tangent_arg(tx, ty, tz, tangent)) return rc;
-  return set_sample_eval_common(plan, call_flags, nx, ny, nz, tx, ty, tz, out_x, out_y, out_z, xi0, xi1, mask, n,
+  return set_sample_eval_common(true, plan, call_flags, nx, ny, nz, tx, ty, tz, out_x, out_y, out_z, xi0, xi1, mask, n,
                                 component, dir_x, dir_y, dir_z, pdf, flag, r, g, b, wr, wg, wb, stream);
 }
 
@@ -1513,9 +1550,7 @@ int bbm_hip_set_plan_gather(const bbm_hip_set_plan* plan, const void* const* fro
   // kSetMaxIn streams a launch; the mask travels with the first
   for (int first = 0; first == 0 || first < count; first += kSetMaxIn)
   {
-    SetMoveArgs m;
-    std::memset(&m, 0, sizeof(m));
-    m.src = plan->src; m.n = plan->n; m.capacity = plan->seg[plan->set->rows.rows];
+    SetMoveArgs m = set_move(*plan);
     for (int c = first; c < count && c < first + kSetMaxIn; ++c) move_in(m, from[c], to[c]);
     if (first == 0) { m.mask_from = mask_from; m.mask_to = mask_to; }
     if (const int rc = batched ? set_gather_launch_batched(m, s) : set_gather_launch(m, s)) return rc;
@@ -1532,9 +1567,7 @@ int bbm_hip_set_plan_scatter(const bbm_hip_set_plan* plan, const void* const* fr
   const hipStream_t s = static_cast<hipStream_t>(stream);
   for (int first = 0; first < count; first += kSetMaxOut)
   {
-    SetMoveArgs m;
-    std::memset(&m, 0, sizeof(m));
-    m.src = plan->src; m.n = plan->n; m.capacity = plan->seg[plan->set->rows.rows];
+    SetMoveArgs m = set_move(*plan);
     for (int c = first; c < count && c < first + kSetMaxOut; ++c) move_out(m, const_cast<void*>(from[c]), to[c]);
     if (const int rc = set_scatter_launch(m, s)) return rc;
   }
@@ -1549,39 +1582,8 @@ int bbm_hip_set_eval_pdf_sorted(const bbm_hip_set_plan* plan, int call_flags,
                                 const uint8_t* mask, size_t slots, uint32_t component, uint32_t unit,
                                 float* r, float* g, float* b, float* pdf, float* cos_in, void* stream)
 {
-  bool tangent, done, world;
-  int rc = tangent_arg(tx, ty, tz, tangent);
-  if (rc) return rc;
-  rc = set_sorted_call(plan, call_flags, slots, done);
-  if (rc || done) return rc;
-  if ((rc = set_normal(nx, ny, nz, world))) return rc;
-  if (tangent && !world) return fail(BBM_HIP_ERR_INVALID_ARG, "tangent needs a normal: it fills the frame of the world-space call");
-  if (cos_in && !world) return fail(BBM_HIP_ERR_INVALID_ARG, "cos_in needs a normal: it is the cosine of `in` against it");
-  EvalArgs checked;
-  int mode = 0;
-  if ((rc = eval_args(mode, in_x, in_y, in_z, out_x, out_y, out_z, mask, slots, component, r, g, b, pdf, checked))) return rc;
-  const bbm_hip_set& set = *plan->set;
-  const uint32_t rows = set.rows.rows;
-  for (uint32_t k = 0; world && k < rows; ++k)
-    if (!set.tables[k]->e->run.eval_pdf_tab_world)
-      return fail(BBM_HIP_ERR_UNSUPPORTED, std::string(set.tables[k]->e->name) + ": no material-table kernels");
-  for (uint32_t k = 0; k < rows; ++k)
-  {
-    const size_t o = plan->seg[k], nk = plan->seg[k + 1] - o;
-    if (nk == 0) continue;
-    const auto in = [o](const float* p) { return p ? p + o : nullptr; };
-    const auto at = [o](float* p) { return p ? p + o : nullptr; };
-    const uint8_t* mk = mask ? mask + o : nullptr;
-    if (world)
-      rc = eval_pdf_table_world_common(set.tables[k], call_flags, plan->local + o, nx + o, ny + o, nz + o, in(tx),
-                                       in(ty), in(tz), in_x + o, in_y + o, in_z + o, out_x + o, out_y + o, out_z + o,
-                                       mk, nk, component, at(r), at(g), at(b), at(pdf), at(cos_in), stream);
-    else
-      rc = bbm_hip_eval_pdf_table(set.tables[k], call_flags, plan->local + o, in_x + o, in_y + o, in_z + o, out_x + o,
-                                  out_y + o, out_z + o, mk, nk, component, unit, at(r), at(g), at(b), at(pdf), stream);
-    if (rc) return rc;
-  }
-  return BBM_HIP_OK;
+  return set_eval_pdf_common(false, plan, call_flags, nx, ny, nz, tx, ty, tz, in_x, in_y, in_z, out_x, out_y, out_z,
+                             mask, slots, component, unit, r, g, b, pdf, cos_in, stream);
 }
 
 int bbm_hip_set_sample_eval_sorted(const bbm_hip_set_plan* plan, int call_flags,
@@ -1594,41 +1596,8 @@ int bbm_hip_set_sample_eval_sorted(const bbm_hip_set_plan* plan, int call_flags,
                                    float* r, float* g, float* b, float* wr, float* wg, float* wb, void* stream)
 {
   (void)unit;
-  bool tangent, done, world;
-  int rc = tangent_arg(tx, ty, tz, tangent);
-  if (rc) return rc;
-  rc = set_sorted_call(plan, call_flags, slots, done);
-  if (rc || done) return rc;
-  if ((rc = set_normal(nx, ny, nz, world))) return rc;
-  if (tangent && !world) return fail(BBM_HIP_ERR_INVALID_ARG, "tangent needs a normal: it fills the frame of the world-space call");
-  SampleEvalArgs checked;
-  if ((rc = sample_eval_args(out_x, out_y, out_z, xi0, xi1, mask, slots, component, dir_x, dir_y, dir_z, pdf, flag,
-                             r, g, b, wr, wg, wb, checked)))
-    return rc;
-  const bbm_hip_set& set = *plan->set;
-  const uint32_t rows = set.rows.rows;
-  for (uint32_t k = 0; k < rows; ++k)
-    if (!set.tables[k]->e->run.sample_eval_tab || (world && !set.tables[k]->e->run.sample_eval_tab_world))
-      return fail(BBM_HIP_ERR_UNSUPPORTED, std::string(set.tables[k]->e->name) + ": no material-table kernels");
-  for (uint32_t k = 0; k < rows; ++k)
-  {
-    const size_t o = plan->seg[k], nk = plan->seg[k + 1] - o;
-    if (nk == 0) continue;
-    const auto in = [o](const float* p) { return p ? p + o : nullptr; };
-    const auto at = [o](float* p) { return p ? p + o : nullptr; };
-    const uint8_t* mk = mask ? mask + o : nullptr;
-    if (world)
-      rc = sample_eval_table_common(true, set.tables[k], call_flags, plan->local + o, nx + o, ny + o, nz + o, in(tx),
-                                    in(ty), in(tz), out_x + o, out_y + o, out_z + o, xi0 + o, xi1 + o, mk, nk,
-                                    component, dir_x + o, dir_y + o, dir_z + o, pdf + o, flag + o, at(r), at(g), at(b),
-                                    at(wr), at(wg), at(wb), stream);
-    else
-      rc = bbm_hip_sample_eval_table(set.tables[k], call_flags, plan->local + o, out_x + o, out_y + o, out_z + o,
-                                     xi0 + o, xi1 + o, mk, nk, component, 0u, dir_x + o, dir_y + o, dir_z + o, pdf + o,
-                                     flag + o, at(r), at(g), at(b), at(wr), at(wg), at(wb), stream);
-    if (rc) return rc;
-  }
-  return BBM_HIP_OK;
+  return set_sample_eval_common(false, plan, call_flags, nx, ny, nz, tx, ty, tz, out_x, out_y, out_z, xi0, xi1, mask,
+                                slots, component, dir_x, dir_y, dir_z, pdf, flag, r, g, b, wr, wg, wb, stream);
 }
 
 // ------------------------------------------------------------------------------- doubleRGB (f64.hip)

@@ -2,7 +2,10 @@
 // lanes belong to different material tables to the table kernels and back.  A plan is the stable partition of the
 // lanes by table ("row"): k_set_count, k_set_scan and k_set_place build it; k_set_gather moves the input streams into
 // per-row segments and k_set_scatter puts the results back.  The kernels are in set.hip; the entry points
-// (bbm_hip_set_*) are in bbm_hip.hip, which calls the table entry points on the segments.  No model knowledge.
+// (bbm_hip_set_*) are in bbm_hip.hip, which calls the table entry points on the segments: one check function and one
+// row loop per call kind (set_eval_pdf_check / _rows, set_sample_eval_check / _rows).  A call in plan order is that
+// loop on the caller's streams; a call in lane order (set_lane_order) is the same loop between a gather into scratch
+// and a scatter out of it, the scratch sized by the streams it entered into the two moves.  No model knowledge.
 #pragma once
 #include <hip/hip_runtime.h>
 
